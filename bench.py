@@ -20,6 +20,13 @@ split counted once, by the rank owning it) / max-over-ranks wall time.
 
 Run: python bench.py [--gpus N --steps K --warmup W]  (N > 1: one process per GPU,
 relaunched under torch.distributed.run unless already launched by it)
+
+A plain run sets up, warms up, times the K passes and prints the result line.
+--dump-outputs DIR also writes what the last timed pass computed (DIR/*.npy).
+--full adds everything else: the per-kernel HIP-event pass and the roofline,
+the final complex checked against the reference's fingerprint (N > 1: the
+halo check and the stitch), the CPU baseline, and the bunny-scale, large-net
+and finish-at-scale legs (--no-cpu leaves the CPU baseline and the legs out).
 """
 import argparse
 import json
@@ -489,6 +496,48 @@ def design_independent_rates(ktime: dict, stats: list) -> dict:
     return out
 
 
+DUMP_ROWS = 1 << 20   # rows kept of a larger output array
+DUMP_SEED = 20240607  # of the row sample (fixed: two builds keep the same rows)
+
+
+def sample_rows(n: int, stream: int):
+    """Sorted row numbers of the fixed sample of an n-row array (None: the
+    array is kept whole)."""
+    if n <= DUMP_ROWS:
+        return None
+    rng = np.random.Generator(np.random.PCG64([DUMP_SEED, stream]))
+    return np.sort(rng.choice(n, DUMP_ROWS, replace=False))
+
+
+def dump_outputs(path: str, eng, stats: list, suffix: str = "") -> None:
+    """What the last timed pass left to its caller, as path/<name>.npy: the
+    compacted complex (Engine.export: vertices float32, edges as float64
+    vertex numbers; of more than DUMP_ROWS rows a fixed seeded sample, the row
+    numbers next to it), its sizes and order-free set hashes (each 64-bit
+    hash as two 32-bit halves, exact in float64), and the pass's per-step
+    counters.  At most 2^20 * (12 + 16 + 8 + 8) bytes = 46 MB."""
+    from tropical._hip import TnpStepStats
+    from tropical.distributed import complex_hash
+    os.makedirs(path, exist_ok=True)
+    V, E, _ = eng.export()
+    hv, he = complex_hash(V, E)
+
+    def save(name, a):
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(a))
+
+    for k, (name, t, dt) in enumerate((("vertices", V, np.float32), ("edges", E, np.float64))):
+        rows = sample_rows(int(t.shape[0]), k)
+        if rows is not None:
+            t = t[torch.from_numpy(rows).to(t.device)]
+            save(name + "_rows", rows.astype(np.float64))
+        save(name, t.cpu().numpy().astype(dt))
+    halves = [float(x) for h in (hv, he) for x in ((h >> 32) & 0xFFFFFFFF, h & 0xFFFFFFFF)]
+    save("complex", np.array([V.shape[0], E.shape[0]] + halves, dtype=np.float64))
+    # the 64-bit plane mask is not a count (and not exact in float64)
+    cols = [k for k, _ in TnpStepStats._fields_ if k != "next_active"]
+    save("step_stats", np.array([[s[k] for k in cols] for s in stats], dtype=np.float64).reshape(len(stats), len(cols)))
+
+
 def chamfer(a: np.ndarray, b: np.ndarray) -> float:
     """chamfer_distance.py:39-48 formula (mean NN L2 both ways / 2)."""
     if len(a) == 0 or len(b) == 0:
@@ -517,7 +566,12 @@ def main():
     # pair materialisation faster than the lattice); 128 is the benchmarked
     # workload itself, ~18 min of the reference's CPU path
     ap.add_argument("--cpu-marks", type=int, default=int(os.environ.get("TNP_CPU_MARKS", 48)))
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: without the CPU baseline and the legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel pass and roofline, the check of the final complex against the "
+                         "reference, the CPU baseline and the bunny-scale / large-net / finish legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass computed as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -618,16 +672,22 @@ def main():
         all_stats.append(one_pass())
     barrier()
     dt = time.perf_counter() - t0
-    # one more pass with a HIP-event pair around every engine launch (kept out
-    # of the timed region: the event records cost host time per launch)
-    eng.kernel_timer(True)
-    one_pass()
-    ktime = eng.kernel_timer(False)
-    barrier()
+    if args.dump_outputs and args.steps > 0:
+        # the engine still holds the last timed pass's complex
+        dump_outputs(args.dump_outputs, eng, all_stats[-1], f"_rank{rank}" if world > 1 else "")
+        barrier()
+    ktime = {}
+    if args.full:
+        # one more pass with a HIP-event pair around every engine launch (kept out
+        # of the timed region: the event records cost host time per launch)
+        eng.kernel_timer(True)
+        one_pass()
+        ktime = eng.kernel_timer(False)
+        barrier()
 
     from tropical.distributed import complex_hash
     stitched = None
-    if world == 1:
+    if args.full and world == 1:
         Vf, Ef, _ = eng.export()
         hv, he = complex_hash(Vf, Ef)
         stitched = {"vertices": int(Vf.shape[0]), "edges": int(Ef.shape[0]),
@@ -640,7 +700,7 @@ def main():
             if got != ref:
                 raise SystemExit(f"final complex {got} differs from the reference's {ref}")
             stitched["matches_reference"] = True
-    else:
+    elif args.full:
         # the complete sharded output: each slab exported, the neighbours'
         # views next to every cut compared (fails loudly if a halo was too
         # narrow), stitched into one global complex (tropical/distributed.py;
@@ -746,9 +806,13 @@ def main():
             # ns per entry / pair test / split / edge, independent of the byte model
             "unit_rates": design_independent_rates(ktime, st0),
         }
+        if not args.full:
+            # a plain run made no HIP-event pass: nothing per kernel to report
+            for k in ("roofline", "kernel_ms_per_pass", "unit_rates"):
+                del out[k]
         if stitched:
             out["final_complex" if world == 1 else "stitched_complex"] = stitched
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             thr = cpu_threads()
             Gc = args.cpu_marks
             log(f"CPU baseline: the oracle on the {Gc}^3 lattice, {thr} threads")
@@ -780,7 +844,7 @@ def main():
                               "timed by tests/golden/make_golden.py when it produced the bench128 golden",
                     "gpu_over_reference": round(value / (per_pass / ref_s), 1)}
             engine_for(net)  # restore
-        if not args.no_cpu and world == 1:
+        if args.full and not args.no_cpu and world == 1:
             log("bunny-scale and large-net legs")
             out["small_net"] = small_net_check(dev, force=True)
             out["small_net_curve"] = small_net_check(dev, force=False)

@@ -9,9 +9,9 @@
 #   tests              every -m gpu test (stop at the first failure)
 #   test:<path>        one test file / node id
 #   smoke              __graft_entry__.smoke()
-#   bench[:G[:lib]]    bench.py --no-cpu at G marks (default 128), 10 timed passes;
+#   bench[:G[:lib]]    bench.py --full --no-cpu at G marks (default 128), 10 timed passes;
 #                      lib: an in-tree variant (TNP_LIB)
-#   benchfull          the default bench line (CPU baseline and legs included)
+#   benchfull          bench.py --full (roofline, CPU baseline and legs included)
 #   sp[:G[:lib]]       tools/step_profile.py G 6 (per-step kernel times)
 #   small[:lib]        tools/small_profile.py (bunny-scale latency)
 #   finish[:lib]       tools/finish_profile.py
@@ -55,8 +55,8 @@ for step in "$@"; do
     tests) run 900 1 python -u -m pytest tests -m gpu -x -q --timeout 200 --timeout-method thread -p no:cacheprovider ;;
     test) run 400 1 python -u -m pytest "$a1" -m gpu -x -v --timeout 200 --timeout-method thread -p no:cacheprovider ;;
     smoke) run 300 0 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run 400 0 env "$(lib "$a2")" python -u bench.py --marks "${a1:-128}" --steps 10 --warmup 3 --no-cpu ;;
-    benchfull) run 900 0 python -u bench.py ;;
+    bench) run 400 0 env "$(lib "$a2")" python -u bench.py --marks "${a1:-128}" --steps 10 --warmup 3 --full --no-cpu ;;
+    benchfull) run 900 0 python -u bench.py --full ;;
     sp) run 300 0 env "$(lib "$a2")" python -u tools/step_profile.py "${a1:-128}" 6 ;;
     small) run 300 0 env "$(lib "$a1")" python -u tools/small_profile.py ;;
     finish) run 300 0 env "$(lib "$a1")" python -u tools/finish_profile.py ;;
@@ -67,13 +67,13 @@ for step in "$@"; do
     pmc) run 120 0 rocprofv3 --pmc ${a1//,/ } -d "gpurun_out/${tag}_pmc_${a1//,/_}" -o run --output-format csv \
             -- python bench.py --marks "${a2:-128}" --steps 1 --warmup 1 --no-cpu ;;
     pmcsession) run 900 0 bash tools/pmc_session.sh ;;
-    rehearsal) run 300 0 python -u bench.py --marks 161 --steps 2 --warmup 1 --no-cpu &&
+    rehearsal) run 300 0 python -u bench.py --marks 161 --steps 2 --warmup 1 --full --no-cpu &&
                run 400 0 env TNP_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
                  --nproc-per-node "${a1:-2}" --master-addr 127.0.0.1 --master-port 29517 bench.py \
-                 --gpus "${a1:-2}" --steps 2 --warmup 1 --no-cpu ;;
+                 --gpus "${a1:-2}" --steps 2 --warmup 1 --full --no-cpu ;;
     ranks) run 400 1 env TNP_DIST_BACKEND=gloo python -m torch.distributed.run --nnodes=1 \
              --nproc-per-node "${a1:-2}" --master-addr 127.0.0.1 --master-port 29518 bench.py \
-             --gpus "${a1:-2}" --steps 2 --warmup 1 --no-cpu ;;
+             --gpus "${a1:-2}" --steps 2 --warmup 1 --full --no-cpu ;;
     diag) run 240 0 python -u tools/descend_diag.py ${a1//,/ } ;;
     env) export "$a1"; echo "== env $a1" >> "$sess" ;;
     *) echo "unknown step $step" >> "$sess"; exit 2 ;;
