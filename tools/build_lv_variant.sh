@@ -2,7 +2,7 @@
 # Experimental library variant of ONE level count's net kernels (net_lv.hip):
 # recompile it with extra defines and link it with the in-tree objects into
 # _lib/libtropical_hip_<name>.so (TNP_LIB=libtropical_hip_<name>.so).
-#   tools/build_lv_variant.sh <name> <levels> "-DTNP_FWD_SHADOW -DTNP_SHAPES_BENCH_ONLY"
+#   tools/build_lv_variant.sh <name> <levels> "-DTNP_SHAPES_BENCH_ONLY"
 set -e
 cd "$(dirname "$0")/../tropical-nerf.pytorch_amd/csrc"
 name=$1; lv=$2; defs=$3

@@ -29,8 +29,6 @@
 // deterministic.  Traffic per entry: 8 B scatter write + 8 B read + 24 B key
 // gather + 32 B record write, against ~70 B for three 8-bit radix passes.
 #include <algorithm>
-#include <cstdlib>
-#include <cstdio>
 
 #include "common.h"
 #include "step.h"
@@ -56,23 +54,6 @@ __device__ __forceinline__ int member_of(const int32_t* members, int64_t S, int6
 }
 
 using BGeom = BucketGeom;
-
-// TNP_BG_PHASES=1 (diagnostic builds, tools/build_variant.sh): per-phase
-// shader-clock totals of k_bucket_group, printed per launch to stderr
-#ifndef TNP_BG_PHASES
-#define TNP_BG_PHASES 0
-#endif
-#if TNP_BG_PHASES
-__device__ unsigned long long g_bg_ph[8 * 8];
-#define BG_PH(k) \
-  do {           \
-    if (threadIdx.x == 0) tph[k] = __builtin_readcyclecounter(); \
-  } while (0)
-#else
-#define BG_PH(k) \
-  do {           \
-  } while (0)
-#endif
 
 // the window pass the grouping kernel runs over each bucket (keys == null:
 // none; the engine then launches k_connect_win)
@@ -703,8 +684,7 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
                                              const ulonglong2* __restrict__ pz, CellEnt* __restrict__ ents,
                                              const PairLists& pl, int64_t* __restrict__ ctr, int* cnt,
                                              int* cur, int64_t* lds, int64_t* lds3, int64_t* s_pk,
-                                             int64_t* s_sp, unsigned long long* tph, void* order) {
-  (void)tph;
+                                             int64_t* s_sp, void* order) {
   constexpr int LC = 1 << (3 * SH);
   for (int i = threadIdx.x; i < LC; i += TNP_BLOCK) cnt[i] = 0;
   __syncthreads();
@@ -721,7 +701,6 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
       if (w[k] != ~0ull) atomicAdd(&cnt[(int)(w[k] >> 40)], 1);
   }
   __syncthreads();
-  BG_PH(1);
   // exclusive scan of cnt into cur (contiguous chunk per thread)
   constexpr int per = LC / TNP_BLOCK > 0 ? LC / TNP_BLOCK : 1;
   const int c0 = threadIdx.x * per;
@@ -734,7 +713,6 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
     run += cnt[i];
   }
   __syncthreads();
-  BG_PH(2);
   // records, cell-contiguous: the member keys gathered here (the members of
   // one bucket are spatially close: their slots cluster).  perm != null
   // (the LDS-record path): the entries' cell order goes to perm[] instead,
@@ -778,7 +756,6 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
     }
   }
   __syncthreads();
-  BG_PH(3);
   // pair cells above WCELL members in local-cell order (cur[i] now = end
   // of cell i); the pairs of the smaller cells are the window pass's
   int npc = 0;
@@ -1225,15 +1202,12 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
       group_small<SH>(b, base, (int)n, ekv, pz, wa, below, ctr, W);
     }
   } else {
-    unsigned long long tph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    BG_PH(0);
     // (a bucket of one chunk gains nothing from it: bunny-scale buckets)
     const bool in_lds = LREC && wa.keys && pl.perm && n > TNP_BG_LDS_MIN && n < 65536;
     void* const order = !in_lds ? nullptr
                                 : SW ? static_cast<void*>(reinterpret_cast<uint64_t*>(pl.perm) + base)
                                      : static_cast<void*>(pl.perm + base);
-    group_bucket<SH>(G, b, base, n, ekv, pz, ents, pl, ctr, cnt, cur, lds, lds3, &s_pk, &s_sp, tph, order);
-    BG_PH(4);
+    group_bucket<SH>(G, b, base, n, ekv, pz, ents, pl, ctr, cnt, cur, lds, lds3, &s_pk, &s_sp, order);
     if (wa.keys) {
       // the window pass over this bucket's records, right behind their
       // stores (the workgroup's own stores: visible after the barrier)
@@ -1262,7 +1236,6 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
         // (every wave has read the cells it bounds by before any list is written)
         __syncthreads();
         const int nw = uniform(build_windows_range(cnt, cur, c_lo, c_hi));
-        BG_PH(5);
         const uint32_t* wl = reinterpret_cast<const uint32_t*>(cnt) + c_lo;
         auto span = [&](int k, int& s, int& m) {
           if (k >= nw) { s = 0; m = 0; return; }
@@ -1348,7 +1321,6 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
           if (tnp::lane() == 0) nwin_s = nw;
         }
         __syncthreads();
-        BG_PH(5);
         if (in_lds) {
           // chunks of TNP_LREC_CH record positions gathered into LDS, then the
           // windows that start there tested.  Software-pipelined: SW (the
@@ -1464,7 +1436,6 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
         window_pass(ents, base, base + n, tnp::wave(), TNP_WAVES, below, wa.nb, wa.fmask, wa.keys, wa.cap,
                     wa.xs, ctr, W, a);
       }
-      BG_PH(6);
       fold_wave_counts(a);
       window_flush(wa.keys, wa.cap, wa.xs, ctr, W, a);
       int64_t tc, tr, tx;
@@ -1472,14 +1443,7 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
       tnp::block_scan_excl(a.n_reg, lds, tr);
       tnp::block_scan_excl(a.n_conn, lds, tx);
       if (threadIdx.x == 0) bucket_stats_out(wa, b, tc, tr, tx, s_sp, ctr);
-      BG_PH(7);
     }
-#if TNP_BG_PHASES
-    if (threadIdx.x == 0)
-      for (int k = 0; k < 7; ++k)
-        if (tph[k + 1] > tph[k] && tph[k])
-          atomicAdd(&g_bg_ph[k * 8 + (blockIdx.x & 7)], tph[k + 1] - tph[k]);
-#endif
   }
 }
 
@@ -1495,22 +1459,13 @@ int bucket_geometry(int n_marks, const int lo[3], const int hi[3], BucketGeom* g
     clo[d] = std::max(0, lo[d]);
     cn[d] = std::min(NC - 1, hi[d] + 3) - clo[d] + 1;
   }
-  static const int s_env = [] {  // TNP_BUCKET_SH=3|4: force the bucket edge (experiments)
-    const char* v = getenv("TNP_BUCKET_SH");
-    return v ? atoi(v) : 0;
-  }();
-  static const int s_sub = [] {  // TNP_BUCKET_SUB=0: never two-level, 1: always (experiments)
-    const char* v = getenv("TNP_BUCKET_SUB");
-    return v ? atoi(v) : -1;
-  }();
-  for (int s = (s_env == 4 || s_sub == 1 ? 4 : 3); s <= 4; ++s) {
+  for (int s = 3; s <= 4; ++s) {
     int nbs[3];
     for (int d = 0; d < 3; ++d) nbs[d] = (cn[d] + (1 << s) - 1) >> s;
     const int64_t nb = (int64_t)nbs[0] * nbs[1] * nbs[2];
     if (nb > BUCKET_MAX) continue;
     // 16^3-cell member buckets are refined into 8^3-cell group buckets
-    // unless TNP_BUCKET_SH=4 asks for the 16^3-cell grouping kernel
-    const int sub = s == 4 && s_env != 4 && s_sub != 0;
+    const int sub = s == 4;
     *g = BucketGeom{NC,          s,           nbs[0],      nbs[1],   nbs[2],   clo[0],
                     clo[1],      clo[2],      nbs[0] << s, nbs[1] << s, nbs[2] << s, (int)nb,
                     sub,         sub ? 8 * (int)nb : (int)nb};
@@ -1532,11 +1487,7 @@ int launch_bucket_entries(const int32_t* members, int64_t S, int64_t V, int64_t 
   if (ovr)
     ov = Override{ovr->flag, ovr->shared, ovr->pre, ovr->ld, ovr->keep_from, ovr->pos, ovr->zero,
                   reinterpret_cast<ulonglong2*>(ovr->pz)};
-  static const bool s_small = [] {  // TNP_SMALL_ENTRIES=0: always the two-launch path (A/B)
-    const char* v = getenv("TNP_SMALL_ENTRIES");
-    return !(v && v[0] == '0');
-  }();
-  if (s_small && M <= SB_MAX_M && (!live || nlive <= SB_MAX_LIVE)) {
+  if (M <= SB_MAX_M && (!live || nlive <= SB_MAX_LIVE)) {
     // bcount / bcur stay untouched (the grouping kernel zeroes them anyway)
     hipLaunchKernelGGL(k_bucket_small, dim3(1), dim3(SB_THREADS), NB * sizeof(int), s, members, S, V, M, keys, zero,
                        idx, G, NB, bbase, ekv, live, nlive, ov, ctr);
@@ -1598,20 +1549,6 @@ int launch_bucket_pairs(const BucketGeom& G, const int64_t* bbase, const uint64_
   else
     hipLaunchKernelGGL((k_bucket_group<4, false>), dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, wa,
                        pl, ctr);
-#if TNP_BG_PHASES
-  {
-    unsigned long long h[64];
-    (void)hipStreamSynchronize(s);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_bg_ph), sizeof(h));
-    unsigned long long t[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int k = 0; k < 7; ++k)
-      for (int x = 0; x < 8; ++x) t[k] += h[k * 8 + x];
-    fprintf(stderr, "bg_phases count %llu scan %llu records %llu paircells %llu windows %llu pass %llu flush %llu\n",
-            t[0], t[1], t[2], t[3], t[4], t[5], t[6]);
-    for (auto& v : h) v = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_bg_ph), h, sizeof(h));
-  }
-#endif
   TNP_CHECK(hipGetLastError());
   return 0;
 }

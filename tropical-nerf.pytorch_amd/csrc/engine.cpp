@@ -212,7 +212,6 @@ struct tnp_engine {
   // with the lazy prune's per-workgroup kept counts -- no count_live launch
   bool defer_counts = false;  // set by the run loop only
   bool cnt_pending = false;
-  bool defer_ok = true;               // TNP_DEFER_COUNTS=0: count in the finish (A/B)
   bool early_forward = true;          // TNP_EARLY_FWD=0: k_forward_new after S is read back (A/B)
   // the early k_forward_new's row bound (early_bound): the largest split
   // count this engine has seen, not the edge-slot count E -- E counts the
@@ -220,19 +219,6 @@ struct tnp_engine {
   // and the shared-plane words keep whatever capacity the bound asks for
   int64_t max_split_seen = 0;
   int64_t n_early_redo = 0;  // steps whose S exceeded the early bound (forward run again)
-  // side stream: the lazy prune of the old edges and e_new runs there, beside
-  // the grouping kernel and the connect on the caller's stream (finish);
-  // ev_s2[0]: the caller's stream reached the prune's inputs, ev_s2[1]: the
-  // prune is done (the caller's stream waits on it before anything touches
-  // the edge slots again: side_join)
-  hipStream_t s2 = nullptr;
-  hipEvent_t ev_s2[2] = {nullptr, nullptr};
-  bool s2_pending = false;
-  // TNP_SIDE_PRUNE=1 at creation: part A on the side stream.  Off: measured
-  // no faster (profiles/r06_ab_side_prune.jsonl: 3.71-3.75 ms per 128^3 pass
-  // either way -- the two kernels slow each other down as much as they
-  // overlap: bucket_group 0.80 -> 1.08 ms, the prune 0.63 -> 1.03 ms)
-  bool side_prune = false;
   bool early_bound_splits = true;  // TNP_EARLY_BOUND=0 at creation: the edge-slot bound E (round 5, A/B)
   // the connecting-edge sort: lo half + run pass for runs of <= sort_run keys
   // (sort.hip sort_keys_lex); 0: all 2 nb bits by onesweep.  TNP_SORT_RUN at creation
@@ -283,9 +269,7 @@ struct tnp_engine {
   Buf sents2;               // ... regrouped by octant (two-level bucket geometries, bk[8]: their bases)
   Buf bk[14];               // bucket.hip scratch (per-bucket counts, bases, pair-cell areas)
   bool radix_cells = false; // TNP_RADIX_CELLS=1: the radix-sort bucketing path
-  bool lazy_edges = true;   // TNP_LAZY_EDGES=0: every pruning step compacts the edge list
   bool lds_records = true;  // TNP_LDS_RECORDS=0: the grouping's records go through memory
-  bool packed_records = true;  // TNP_PACKED_RECORDS=0: the LDS records stay 32-B CellEnt
   bool bk_clean = false;    // bucket counters (bk[0], bk[1]) are zero
   Buf cv[CV_N];
 };
@@ -587,8 +571,8 @@ static int compact_edges(tnp_engine* e, hipStream_t s) {
   TIMED("compact_edges", 12.0 * E,
         launch_prune_lb(P<int32_t>(e->edges), E, nullptr, 0, e->V, nullptr, 0, 0, -1, e->K - 1,
                         P<uint64_t>(e->cur.pz), P<uint8_t>(e->edm), P<uint8_t>(e->eef), P<int32_t>(e->edges_alt),
-                        P<uint8_t>(e->edm_alt), P<uint8_t>(e->eef_alt), P<uint8_t>(e->live), false,
-                        P<int64_t>(e->ctr), lb, s));
+                        P<uint8_t>(e->edm_alt), P<uint8_t>(e->eef_alt), P<uint8_t>(e->live), P<int64_t>(e->ctr),
+                        lb, s));
   std::swap(e->edges, e->edges_alt);
   std::swap(e->edm, e->edm_alt);
   std::swap(e->eef, e->eef_alt);
@@ -654,15 +638,11 @@ extern "C" int tnp_engine_create(tnp_engine** out, int device) {
   e->device = device;
   if (const char* lim = getenv("TNP_MAX_PAIR_TESTS")) e->max_pair_tests = atoll(lim);
   if (const char* rc = getenv("TNP_RADIX_CELLS")) e->radix_cells = atoi(rc) != 0;
-  if (const char* lz = getenv("TNP_LAZY_EDGES")) e->lazy_edges = atoi(lz) != 0;
   if (const char* lr = getenv("TNP_LDS_RECORDS")) e->lds_records = atoi(lr) != 0;
-  if (const char* pr = getenv("TNP_PACKED_RECORDS")) e->packed_records = atoi(pr) != 0;
   if (const char* sp = getenv("TNP_LB_SPIN")) e->lb_spin = atoi(sp);
-  if (const char* dc = getenv("TNP_DEFER_COUNTS")) e->defer_ok = atoi(dc) != 0;
   if (const char* ef = getenv("TNP_EARLY_FWD")) e->early_forward = atoi(ef) != 0;
   if (const char* eb = getenv("TNP_EARLY_BOUND")) e->early_bound_splits = atoi(eb) != 0;
   if (const char* sr = getenv("TNP_SORT_RUN")) e->sort_run = atoi(sr);
-  if (const char* sp = getenv("TNP_SIDE_PRUNE")) e->side_prune = atoi(sp) != 0;
   if (hipHostMalloc((void**)&e->h_ctr, CTR_N * sizeof(int64_t), hipHostMallocDefault) != hipSuccess ||
       hipHostMalloc((void**)&e->h_map, 32 * sizeof(int64_t), hipHostMallocMapped | hipHostMallocCoherent) !=
           hipSuccess ||
@@ -703,9 +683,6 @@ extern "C" void tnp_engine_destroy(tnp_engine* e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
   (void)hipDeviceSynchronize();
-  if (e->s2) (void)hipStreamDestroy(e->s2);
-  for (hipEvent_t ev : e->ev_s2)
-    if (ev) (void)hipEventDestroy(ev);
   hipStream_t s = 0;
   for_each_buf(e, [&](Buf& b) { buf_free(b, s); });
   (void)hipDeviceSynchronize();
@@ -1449,85 +1426,60 @@ extern "C" int tnp_engine_split(tnp_engine* e, int idx, void* stream, int64_t* S
   return 0;
 }
 
-// the side stream (created on first use, non-blocking: no implicit sync
-// with the caller's stream) and its two events
-static int side_stream(tnp_engine* e) {
-  if (e->s2) return 0;
-  TNP_CHECK(hipStreamCreateWithFlags(&e->s2, hipStreamNonBlocking));
-  for (hipEvent_t& ev : e->ev_s2) TNP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  return 0;
-}
-// the caller's stream waits for the side stream's prune (every exit of a
-// finish that launched one, errors included)
-static void side_join(tnp_engine* e, hipStream_t s) {
-  if (!e->s2_pending) return;
-  (void)hipStreamWaitEvent(s, e->ev_s2[1], 0);
-  e->s2_pending = false;
-}
-struct SideJoin {
-  tnp_engine* e;
-  hipStream_t s;
-  ~SideJoin() { side_join(e, s); }
+// what the phases of one tnp_engine_finish share (built by the driver)
+struct FinishStep {
+  int idx, prune, override_;
+  int64_t V, E, S, NV;  // vertex slots, edge slots, kept splits, V + S
+  int64_t E_live;       // live edges on entry
+  // set by finish_members: members, the bounds of their cell entries and
+  // pair cells, k_connect's chunk-table capacity
+  int64_t M, TB, RC, bcap;
+  int nb;               // bits of a vertex slot in a connecting-edge key
+  BucketGeom bg;
+  bool buckets, hits_done;
+  int64_t hoff;
+  // out: hit members, cell entries, kept connecting edges; the workgroup
+  // parts of the in-stream part-A prune; the prune is the lazy one
+  int64_t H, T, X;
+  int part_a;
+  bool lazy;
+  // out (finish_prune): the state the driver commits
+  int64_t V_out, E_out, E_live_out;
+  int next_valid;
+  bool defer;  // the live counts left to the next split (tnp_engine_run_steps)
 };
 
-extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override_, void* stream,
-                                 tnp_step_stats* st) {
-  hipStream_t s = (hipStream_t)stream;
-  TNP_CHECK(hipSetDevice(e->device));
-  if (e->pend_idx != idx) { tnp_set_error("finish(%d) without split(%d)", idx, idx); return -1; }
-  if (require_valid(e, "finish")) return -1;
-  if (e->cnt_pending) {  // (the split resolves them; a finish never sees them pending)
-    tnp_set_error("finish(%d): live counts of the last step still pending", idx);
-    return -1;
-  }
-  e->pend_idx = -1;
-  e->valid = false;  // until this step has completed
-  const SideJoin side_guard{e, s};
-  const bool hits_done = e->pend_hits;
-  const int64_t hoff = hits_done ? e->pend_hoff : -1;
-  e->pend_hits = false;
-  const float eps = e->net.eps;
-  const int K = e->K;
-  int64_t S_kept = e->pend_S;
-  if (e->curve) {
-    if (curve_filter(e, idx, override_, s, &S_kept)) return -1;
-    e->masks_valid = false;  // the filter rewired the kept split edges
-    // the kept splits another shard owns (read back with the connect
-    // counters; the split's CTR_DUP count is the flat path's)
-    TNP_CHECK(hipMemsetAsync(P<int64_t>(e->ctr) + CTR_DUP, 0, sizeof(int64_t), s));
-    if (launch_count_unowned(P<uint64_t>(e->cur.grid) + e->V, S_kept, e->own, P<int64_t>(e->ctr), s))
-      return -1;
-  }
-  const int64_t V = e->V, E = e->E, S = S_kept;
-  const int64_t NV = V + S;
+// 1. override + keys of the new vertices (flat bucket path: the override
+//    runs inside the bucket count, finish_buckets)
+static int finish_new_keys(tnp_engine* e, const FinishStep& f, hipStream_t s) {
+  if (e->pend_fused && f.buckets) return 0;
+  const int64_t V = f.V, S = f.S;
+  const int override_ = f.override_, K = e->K;
   VSet& c = e->cur;
-  const float* col = P<float>(c.pre) + (int64_t)idx * c.cap;
   int64_t* ctr = P<int64_t>(e->ctr);
   uint64_t* pos = VP(c, e->kw);
   uint64_t* zero = VZ(c, e->kw);
-  uint64_t* grid = P<uint64_t>(c.grid);
-
-  BucketGeom bg{};
-  int sp0[3], sp1[3];
-  span_of(e, sp0, sp1);
-  const bool buckets = uses_buckets(e, &bg);
-  const int NB = buckets ? bg.NB : 0;
-  // 1. override + keys of the new vertices (flat bucket path: the override
-  //    runs inside the bucket count, below)
-  if (e->pend_fused && buckets) {
-  } else if (e->pend_fused) {
+  if (e->pend_fused) {
     TIMED("override_new", 8.0 * S,
           launch_override_new(S, override_, P<uint64_t>(e->shared), P<float>(c.pre), c.cap,
                               e->pend_keep, V, pos, zero, ctr, P<uint64_t>(c.pz), e->kw, s));
   } else {
     TIMED("finalize_new", (8.0 + 4.0 * K + 4.0 * (K - e->valid_from) + 16.0) * S,
-          launch_finalize_new(S, K, override_, P<uint64_t>(e->shared), P<float>(e->stage), eps,
+          launch_finalize_new(S, K, override_, P<uint64_t>(e->shared), P<float>(e->stage), e->net.eps,
                               P<float>(c.pre), c.cap, e->valid_from, V, pos, zero, ctr,
                               P<uint64_t>(c.pz), e->kw, s));
   }
+  return 0;
+}
 
-  // 2. members = new vertices ++ live hit vertices (any order); the bucket
-  //    path reads the new vertices as slots V.. without a list
+// 2. members = new vertices ++ live hit vertices (any order); the bucket
+//    path reads the new vertices as slots V.. without a list.  Sets M, TB, RC
+//    and bcap, and sizes the buffers of the members' cell entries
+static int finish_members(tnp_engine* e, FinishStep& f, hipStream_t s) {
+  const int64_t V = f.V, S = f.S, NV = f.NV;
+  const bool hits_done = f.hits_done, buckets = f.buckets;
+  const float* col = P<float>(e->cur.pre) + (int64_t)f.idx * e->cur.cap;
+  int64_t* ctr = P<int64_t>(e->ctr);
   if (buf_ensure(e->members, std::max<int64_t>(NV, 1) * sizeof(int32_t), s, hits_done)) return -1;
   if (hits_done) {
     if (!buckets && launch_new_members(P<int32_t>(e->members), S, V, s)) return -1;
@@ -1535,15 +1487,10 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     TIMED("hits", 5.0 * V + 4.0 * S,
           launch_hits(col, P<uint8_t>(e->live), V, e->net.eps_s, P<int32_t>(e->members), S, ctr, s));
   }
-
-  // 3. bucket members by grid cell (dense cell grid over the marks): one
-  //    (cell, member) entry per spanned cell, radix-sorted by cell
-  const int NC = e->net.n_marks + 2;
-  if (NC > 1023) {  // connect packs cell coordinates in 10 bits each
+  if (e->net.n_marks + 2 > 1023) {  // connect packs cell coordinates in 10 bits each
     tnp_set_error("more than 1021 marks per axis");
     return -1;
   }
-  const int64_t ncell = (int64_t)NC * NC * NC;
   // the live member count sizes the span pass and its scan (V counts every
   // slot, live or dead: sizing by it would scan ~V elements per step)
   if (!hits_done && read_ctr(e, s)) return -1;  // else: H came back with S
@@ -1552,114 +1499,209 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
   // buffers take the bound 8 M, so nothing waits for the entry count T
   const int64_t TB = std::max<int64_t>(8 * M, 1);
   const int64_t RC = TB / 2 + 1;  // a pair cell holds >= 2 entries
+  f.M = M;
+  f.TB = TB;
+  f.RC = RC;
   if (buf_ensure(e->ents, TB * cell_ent_bytes(e->kw), s)) return -1;
   if (buf_ensure(e->pcell, RC * sizeof(int32_t), s)) return -1;
   if (buf_ensure(e->pent, RC * sizeof(int32_t), s)) return -1;
   if (buf_ensure(e->pcn, RC * sizeof(int32_t), s)) return -1;
   if (buf_ensure(e->ptoff, RC * sizeof(int64_t), s)) return -1;
-  int64_t H = 0, T = 0;
   // k_connect's chunk table: its capacity is kept across steps (grown on
   // overflow and redone); the bucket path fills it in its pair-cell gather
-  int64_t bcap = std::max<int64_t>(e->bcell.bytes / sizeof(int32_t), 4096);
-  if (buf_ensure(e->bcell, bcap * sizeof(int32_t), s)) return -1;
-  if (buckets) {
-    // spatial buckets, every count on the device (bucket.hip)
-    void* const bk0 = e->bk[0].p;
-    void* const bk1 = e->bk[1].p;
-    if (buf_ensure(e->bk[0], (NB + 1) * sizeof(int32_t), s)) return -1;  // counts (+1: read in pairs)
-    if (buf_ensure(e->bk[1], NB * sizeof(int32_t), s)) return -1;        // cursors
-    if (e->bk[0].p != bk0 || e->bk[1].p != bk1) e->bk_clean = false;     // fresh memory
-    if (buf_ensure(e->bk[2], (NB + 1) * sizeof(int64_t), s)) return -1;  // bases
-    // block parts: one per workgroup of the member passes (the grid is at least
-    // FUSE_MAX_BLOCKS = 512 when the live-flag zeroing rides along)
-    if (buf_ensure(e->bk[7], (std::max<int64_t>(bucket_member_blocks(M), 512) + 2) * sizeof(int64_t), s))
-      return -1;
-    if (buf_ensure(e->sents, TB * sizeof(uint64_t), s)) return -1;
-    // a pruning step recomputes the live flags: zeroed by the bucket count
-    // (after the hit pass read them), re-marked by the prune
-    if (prune && buf_ensure(e->live, std::max<int64_t>(NV + 4, 16), s)) return -1;
-    NewOverride nov{override_, P<uint64_t>(e->shared), P<float>(c.pre), c.cap, e->pend_keep, pos, zero,
-                    P<uint64_t>(c.pz)};
-    TIMED("bucket_entries", 16.0 * M,  // + 8 B per entry, set once T is known
-          // (member m >= S is members[m]: the hits sit at hoff >= S when the split found them)
-          launch_bucket_entries(P<int32_t>(e->members) + (hoff >= 0 ? hoff - S : 0), S, V, M, grid, zero, idx, bg,
-                                P<int32_t>(e->bk[0]), P<int32_t>(e->bk[1]), P<int64_t>(e->bk[2]),
-                                P<int64_t>(e->bk[7]), P<uint64_t>(e->sents), e->bk_clean,
-                                prune ? P<uint8_t>(e->live) : nullptr, NV, e->pend_fused ? &nov : nullptr,
-                                ctr, s));
-    e->bk_clean = false;  // until the grouping's pair-cell gather has reset the counters
-    if (bg.sub) {
-      // two-level geometry: the 16^3-cell buckets split into their 8^3-cell
-      // octants (the grouping's buckets); the refine resets the counters
-      if (buf_ensure(e->bk[8], ((int64_t)bg.NG + 1) * sizeof(int64_t), s)) return -1;
-      if (buf_ensure(e->sents2, TB * sizeof(uint64_t), s)) return -1;
-      TIMED("bucket_refine", 24.0 * M,  // 8 B read twice + 8 B written per entry (set once T is known)
-            launch_bucket_refine(bg, P<int64_t>(e->bk[2]), P<uint64_t>(e->sents), P<int64_t>(e->bk[8]),
-                                 P<uint64_t>(e->sents2), P<int32_t>(e->bk[0]), P<int32_t>(e->bk[1]), s));
+  f.bcap = std::max<int64_t>(e->bcell.bytes / sizeof(int32_t), 4096);
+  if (buf_ensure(e->bcell, f.bcap * sizeof(int32_t), s)) return -1;
+  return 0;
+}
+
+// 3. bucket members by grid cell (dense cell grid over the marks): one
+//    (cell, member) entry per spanned cell.
+//    Spatial buckets, every count on the device (bucket.hip)
+static int finish_buckets(tnp_engine* e, const FinishStep& f, hipStream_t s) {
+  const int idx = f.idx, prune = f.prune, override_ = f.override_;
+  const int64_t V = f.V, S = f.S, NV = f.NV, M = f.M, TB = f.TB, hoff = f.hoff;
+  const BucketGeom& bg = f.bg;
+  const int NB = bg.NB;
+  VSet& c = e->cur;
+  int64_t* ctr = P<int64_t>(e->ctr);
+  uint64_t* pos = VP(c, e->kw);
+  uint64_t* zero = VZ(c, e->kw);
+  uint64_t* grid = P<uint64_t>(c.grid);
+  void* const bk0 = e->bk[0].p;
+  void* const bk1 = e->bk[1].p;
+  if (buf_ensure(e->bk[0], (NB + 1) * sizeof(int32_t), s)) return -1;  // counts (+1: read in pairs)
+  if (buf_ensure(e->bk[1], NB * sizeof(int32_t), s)) return -1;        // cursors
+  if (e->bk[0].p != bk0 || e->bk[1].p != bk1) e->bk_clean = false;     // fresh memory
+  if (buf_ensure(e->bk[2], (NB + 1) * sizeof(int64_t), s)) return -1;  // bases
+  // block parts: one per workgroup of the member passes (the grid is at least
+  // FUSE_MAX_BLOCKS = 512 when the live-flag zeroing rides along)
+  if (buf_ensure(e->bk[7], (std::max<int64_t>(bucket_member_blocks(M), 512) + 2) * sizeof(int64_t), s))
+    return -1;
+  if (buf_ensure(e->sents, TB * sizeof(uint64_t), s)) return -1;
+  // a pruning step recomputes the live flags: zeroed by the bucket count
+  // (after the hit pass read them), re-marked by the prune
+  if (prune && buf_ensure(e->live, std::max<int64_t>(NV + 4, 16), s)) return -1;
+  NewOverride nov{override_, P<uint64_t>(e->shared), P<float>(c.pre), c.cap, e->pend_keep, pos, zero,
+                  P<uint64_t>(c.pz)};
+  TIMED("bucket_entries", 16.0 * M,  // + 8 B per entry, set once T is known
+        // (member m >= S is members[m]: the hits sit at hoff >= S when the split found them)
+        launch_bucket_entries(P<int32_t>(e->members) + (hoff >= 0 ? hoff - S : 0), S, V, M, grid, zero, idx, bg,
+                              P<int32_t>(e->bk[0]), P<int32_t>(e->bk[1]), P<int64_t>(e->bk[2]),
+                              P<int64_t>(e->bk[7]), P<uint64_t>(e->sents), e->bk_clean,
+                              prune ? P<uint8_t>(e->live) : nullptr, NV, e->pend_fused ? &nov : nullptr,
+                              ctr, s));
+  e->bk_clean = false;  // until the grouping's pair-cell gather has reset the counters
+  if (bg.sub) {
+    // two-level geometry: the 16^3-cell buckets split into their 8^3-cell
+    // octants (the grouping's buckets); the refine resets the counters
+    if (buf_ensure(e->bk[8], ((int64_t)bg.NG + 1) * sizeof(int64_t), s)) return -1;
+    if (buf_ensure(e->sents2, TB * sizeof(uint64_t), s)) return -1;
+    TIMED("bucket_refine", 24.0 * M,  // 8 B read twice + 8 B written per entry (set once T is known)
+          launch_bucket_refine(bg, P<int64_t>(e->bk[2]), P<uint64_t>(e->sents), P<int64_t>(e->bk[8]),
+                               P<uint64_t>(e->sents2), P<int32_t>(e->bk[0]), P<int32_t>(e->bk[1]), s));
+  }
+  return 0;
+}
+
+// 3. (fallback) the entries radix-sorted by cell: grids finer than the bucket
+//    geometry, TNP_RADIX_CELLS=1
+static int finish_radix_cells(tnp_engine* e, FinishStep& f, hipStream_t s) {
+  const int idx = f.idx;
+  const int64_t S = f.S, M = f.M, TB = f.TB;
+  int64_t& H = f.H;
+  int64_t& T = f.T;
+  const int NC = e->net.n_marks + 2;
+  const int64_t ncell = (int64_t)NC * NC * NC;
+  VSet& c = e->cur;
+  int64_t* ctr = P<int64_t>(e->ctr);
+  uint64_t* zero = VZ(c, e->kw);
+  uint64_t* grid = P<uint64_t>(c.grid);
+  if (buf_ensure(e->spcnt, std::max<int64_t>(M, 1) * sizeof(int32_t), s)) return -1;
+  if (buf_ensure(e->spoff, std::max<int64_t>(M, 1) * sizeof(int64_t), s)) return -1;
+  if (buf_ensure(e->part, (int64_t)(tnp_grid(M) + 1) * sizeof(int64_t), s)) return -1;
+  TIMED("span_count", 28.0 * M,
+        launch_span_count(P<int32_t>(e->members), S, M, grid, zero, idx, P<int32_t>(e->spcnt),
+                          P<int64_t>(e->part), ctr, e->kw, s));
+  if (scan_counts(e, P<int32_t>(e->spcnt), P<int64_t>(e->spoff), M, CTR_T, s)) return -1;
+  if (buf_ensure(e->ekey_a, TB * sizeof(uint32_t), s)) return -1;
+  if (buf_ensure(e->ent_v, TB * sizeof(int32_t), s)) return -1;
+  if (buf_ensure(e->ekey_b, TB * sizeof(uint32_t), s)) return -1;
+  if (buf_ensure(e->eval_b, TB * sizeof(int32_t), s)) return -1;
+  TIMED("span_emit", 28.0 * M,
+        launch_span_emit(P<int32_t>(e->members), S, M, grid, NC, P<int64_t>(e->spoff),
+                         P<uint32_t>(e->ekey_a), P<int32_t>(e->ent_v), ctr, s));
+  if (read_ctr(e, s)) return -1;
+  if (e->h_ctr[CTR_K0]) {
+    // the reference builds torch.cartesian_prod() of zero tensors (subpoly.py:317)
+    tnp_set_error("meshgrid expects a non-empty TensorList (a region row without zeros, plane %d)", idx);
+    return -1;
+  }
+  H = e->h_ctr[CTR_H];
+  T = e->h_ctr[CTR_T];
+  const int64_t T1 = std::max<int64_t>(T, 1);
+  ktimer_set_bytes(e, 20.0 * M + 8.0 * T);  // span_emit's bytes, known only now
+  int cbits = 1;
+  while (cbits < 32 && (1ll << cbits) < ncell) ++cbits;
+  uint32_t* skey = nullptr;
+  int32_t* sval = nullptr;
+  {
+    size_t need = sort_pairs_scratch_bytes(T, cbits);
+    if (buf_ensure(e->sort_scr2, std::max<size_t>(need, 16), s)) return -1;
+    TIMED("cell_sort", 16.0 * T * ((cbits + 7) / 8),
+          sort_pairs_u32(P<uint32_t>(e->ekey_a), P<uint32_t>(e->ekey_b), P<int32_t>(e->ent_v),
+                         P<int32_t>(e->eval_b), T, cbits, e->sort_scr2.p, e->sort_scr2.bytes, &skey,
+                         &sval, s));
+  }
+  // cells holding member pairs straight from the runs of the sorted keys
+  // (compacted, with their flattened pair space offsets; total = tests)
+  {
+    if (buf_ensure(e->rstart, (T1 + 1) * sizeof(int32_t), s)) return -1;
+    if (T > 0) {
+      TnpLB la, lr, lp;
+      if (lb_begin(e, run_tiles(T), s, &la, 0)) return -1;
+      TIMED("run_starts", 8.0 * T,
+            launch_run_starts(skey, T, P<int32_t>(e->rstart), ctr, la, s));
+      const int64_t pt = pair_run_tiles(T);
+      if (lb_begin(e, pt, s, &lr, 0) || lb_begin(e, pt, s, &lp, 1)) return -1;
+      TIMED("pair_cells", 0.0,
+            launch_pair_runs(skey, P<int32_t>(e->rstart), T, P<int32_t>(e->pcell), P<int32_t>(e->pent),
+                             P<int32_t>(e->pcn), P<int64_t>(e->ptoff), ctr, lr, lp, s));
     }
-  } else {
-    // radix-sort path (grids finer than the bucket geometry, TNP_RADIX_CELLS=1)
-    if (buf_ensure(e->spcnt, std::max<int64_t>(M, 1) * sizeof(int32_t), s)) return -1;
-    if (buf_ensure(e->spoff, std::max<int64_t>(M, 1) * sizeof(int64_t), s)) return -1;
-    if (buf_ensure(e->part, (int64_t)(tnp_grid(M) + 1) * sizeof(int64_t), s)) return -1;
-    TIMED("span_count", 28.0 * M,
-          launch_span_count(P<int32_t>(e->members), S, M, grid, zero, idx, P<int32_t>(e->spcnt),
-                            P<int64_t>(e->part), ctr, e->kw, s));
-    if (scan_counts(e, P<int32_t>(e->spcnt), P<int64_t>(e->spoff), M, CTR_T, s)) return -1;
-    if (buf_ensure(e->ekey_a, TB * sizeof(uint32_t), s)) return -1;
-    if (buf_ensure(e->ent_v, TB * sizeof(int32_t), s)) return -1;
-    if (buf_ensure(e->ekey_b, TB * sizeof(uint32_t), s)) return -1;
-    if (buf_ensure(e->eval_b, TB * sizeof(int32_t), s)) return -1;
-    TIMED("span_emit", 28.0 * M,
-          launch_span_emit(P<int32_t>(e->members), S, M, grid, NC, P<int64_t>(e->spoff),
-                           P<uint32_t>(e->ekey_a), P<int32_t>(e->ent_v), ctr, s));
-    if (read_ctr(e, s)) return -1;
+  }
+  TIMED("entry_keys", 52.0 * T,
+        launch_entry_keys(sval, skey, NC, T, grid, P<uint64_t>(c.pz), e->ents.p, e->kw, s));
+  return 0;
+}
+
+// the counters one connect attempt published: the bucket path's entry
+// errors and counts, the pair tests TT and the kept keys X
+static int connect_counts(tnp_engine* e, FinishStep& f, int64_t* TT_out) {
+  const int idx = f.idx;
+  const int64_t M = f.M;
+  const BucketGeom& bg = f.bg;
+  int64_t& H = f.H;
+  int64_t& T = f.T;
+  int64_t& X = f.X;
+  if (f.buckets) {
+    int sp0[3], sp1[3];
+    span_of(e, sp0, sp1);
+    // the atomically allocated pair-cell list: cells | pairs << 24
+    e->h_ctr[CTR_R] = e->h_ctr[CTR_PCK] & (PCK_CELLS - 1);
+    e->h_ctr[CTR_TESTS] = e->h_ctr[CTR_PCK] >> 24;
+    if (e->h_ctr[CTR_K0] & 2) {
+      tnp_set_error("plane %d: a vertex outside the mark planes [%d, %d] x [%d, %d] x [%d, %d] the engine "
+                    "was given (tnp_engine_set_span)", idx, sp0[0], sp1[0], sp0[1], sp1[1], sp0[2], sp1[2]);
+      return -1;
+    }
     if (e->h_ctr[CTR_K0]) {
       // the reference builds torch.cartesian_prod() of zero tensors (subpoly.py:317)
-      tnp_set_error("meshgrid expects a non-empty TensorList (a region row without zeros, plane %d)", idx);
+      tnp_set_error("meshgrid expects a non-empty TensorList (a region row without zeros, plane %d)",
+                    idx);
       return -1;
     }
     H = e->h_ctr[CTR_H];
     T = e->h_ctr[CTR_T];
-    const int64_t T1 = std::max<int64_t>(T, 1);
-    ktimer_set_bytes(e, 20.0 * M + 8.0 * T);  // span_emit's bytes, known only now
-    int cbits = 1;
-    while (cbits < 32 && (1ll << cbits) < ncell) ++cbits;
-    uint32_t* skey = nullptr;
-    int32_t* sval = nullptr;
-    {
-      size_t need = sort_pairs_scratch_bytes(T, cbits);
-      if (buf_ensure(e->sort_scr2, std::max<size_t>(need, 16), s)) return -1;
-      TIMED("cell_sort", 16.0 * T * ((cbits + 7) / 8),
-            sort_pairs_u32(P<uint32_t>(e->ekey_a), P<uint32_t>(e->ekey_b), P<int32_t>(e->ent_v),
-                           P<int32_t>(e->eval_b), T, cbits, e->sort_scr2.p, e->sort_scr2.bytes, &skey,
-                           &sval, s));
-    }
-    // cells holding member pairs straight from the runs of the sorted keys
-    // (compacted, with their flattened pair space offsets; total = tests)
-    {
-      if (buf_ensure(e->rstart, (T1 + 1) * sizeof(int32_t), s)) return -1;
-      if (T > 0) {
-        TnpLB la, lr, lp;
-        if (lb_begin(e, run_tiles(T), s, &la, 0)) return -1;
-        TIMED("run_starts", 8.0 * T,
-              launch_run_starts(skey, T, P<int32_t>(e->rstart), ctr, la, s));
-        const int64_t pt = pair_run_tiles(T);
-        if (lb_begin(e, pt, s, &lr, 0) || lb_begin(e, pt, s, &lp, 1)) return -1;
-        TIMED("pair_cells", 0.0,
-              launch_pair_runs(skey, P<int32_t>(e->rstart), T, P<int32_t>(e->pcell), P<int32_t>(e->pent),
-                               P<int32_t>(e->pcn), P<int64_t>(e->ptoff), ctr, lr, lp, s));
-      }
-    }
-    TIMED("entry_keys", 52.0 * T,
-          launch_entry_keys(sval, skey, NC, T, grid, P<uint64_t>(c.pz), e->ents.p, e->kw, s));
+    // entries: written once by the scatter; the grouping reads them, gathers
+    // 16 B of member keys and writes the 32 B record; the window pass reads
+    // every record (once, algorithmically) and writes the kept keys
+    ktimer_set_bytes(e, "bucket_entries", 16.0 * M + 8.0 * T);
+    if (bg.sub) ktimer_set_bytes(e, "bucket_refine", 24.0 * T);
+    // the window pass re-reads the records the same workgroup just wrote
+    // (cache traffic): its compulsory bytes are the kept keys.  LDS-record
+    // path: 8 B entry word + 16 B member keys + 4 + 4 B cell order (written,
+    // read back) per entry, records in memory only for k_connect's cells
+    // (not counted: an understatement)
+    ktimer_set_bytes(e, "bucket_group", (e->lds_records ? 32.0 : 56.0) * T + 8.0 * e->h_ctr[CTR_XK]);
   }
-  // 4. connecting edges: test every in-cell member pair once, append the
-  //    emitted ones, radix-sort them (lexicographic c_new, subpoly.py:243-244).
-  //    The pair count stays on the device; the chunk table and the key buffer
-  //    keep their capacity across steps and grow (then redo) on overflow.
-  int nb = 1;
-  while (nb < 31 && (1ll << nb) < NV) ++nb;
+  const int64_t TT = e->h_ctr[CTR_TESTS];
+  X = e->h_ctr[CTR_XK];
+  ktimer_set_bytes(e, 32.0 * TT + 8.0 * T);  // known only now
+  if (e->h_ctr[CTR_BIG] || TT > e->max_pair_tests) {
+    // one linear region holding ~sqrt(2*tests) vertices: the reference would
+    // materialise every in-region pair (subpoly.py:505-518) and run out of
+    // memory long before; refuse instead of grinding for hours
+    tnp_set_error("degenerate complex at plane %d: %lld in-cell vertex pairs exceed the limit %lld "
+                  "(TNP_MAX_PAIR_TESTS)", idx, (long long)TT, (long long)e->max_pair_tests);
+    return -1;
+  }
+  *TT_out = TT;
+  return 0;
+}
+
+// 4. connecting edges: test every in-cell member pair once, append the
+//    emitted ones, radix-sort them (lexicographic c_new, subpoly.py:243-244).
+//    The pair count stays on the device; the chunk table and the key buffer
+//    keep their capacity across steps and grow (then redo) on overflow.
+static int finish_connect(tnp_engine* e, FinishStep& f, hipStream_t s) {
+  const int idx = f.idx, prune = f.prune, nb = f.nb, K = e->K;
+  const int64_t V = f.V, E = f.E, S = f.S, NV = f.NV, M = f.M, TB = f.TB, RC = f.RC;
+  const BucketGeom& bg = f.bg;
+  const bool buckets = f.buckets;
+  const int NC = e->net.n_marks + 2;
+  int64_t bcap = f.bcap;
+  int64_t& X = f.X;
+  VSet& c = e->cur;
+  int64_t* ctr = P<int64_t>(e->ctr);
   // connecting edges this step's pruning drops are never appended (sorted,
   // re-tested): keep_edge() depends on the endpoints only
   const uint64_t cfmask = prune ? prune_mask(idx, K - 1) : 0ull;
@@ -1674,14 +1716,13 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
   if (buckets && !shard && buf_ensure(e->bk[3], (int64_t)NG * 4 * sizeof(int64_t), s)) return -1;
   int64_t* const bstat = (buckets && !shard) ? P<int64_t>(e->bk[3]) : nullptr;
   int64_t cap = connect_key_cap(e->ckeys_a.bytes, M, XS_N);
-  int64_t X = 0, TT = 0;
+  int64_t TT = 0;
   bool chunks_ok = false;  // (radix path) the chunk table matches the pair cells
   // lazy edge deletion (k_prune_lazy) unless the list is mostly dead edges
   // already: then the compacting prune drops them (and this step's)
   // (split-eps mode: always lazy -- its first split planes are recomputed
   // over the edge slots in place, k_ef_cache)
-  const int64_t E_live_in = e->E_live;
-  const bool lazy = prune && (eps2(e) || (e->lazy_edges && (E - E_live_in) <= E_live_in));
+  const bool lazy = prune && (eps2(e) || (E - f.E_live) <= f.E_live);
   // the lazy prune's old edges and e_new need no connecting edge: they are
   // pruned while the connect counts travel to the host (slots [0, E + S)),
   // c_new after the sort (part A's workgroup parts first in lzpart)
@@ -1692,10 +1733,8 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
   // the new vertices (forward_new; their override came with the bucket
   // count) and writes the slots' bytes, e_new and the live flags the bucket
   // count zeroed -- nothing the grouping, the connect, the key sort or their
-  // counters touch.  So it runs on the side stream from here, beside them
-  // (the grouping kernel issue-bound, the prune memory-bound), and the
-  // caller's stream waits for it before the pruning of c_new (side_join)
-  const bool side = early_prune && e->side_prune;
+  // counters touch.  So it is enqueued behind the connect's counter publish
+  // and runs while the counts travel to the host
   if (early_prune) {
     if (buf_ensure(e->live, std::max<int64_t>(NV + 4, 16), s)) return -1;  // (+4: word atomics)
     if (buf_ensure(e->edges, std::max<int64_t>(ES, 1) * 2 * sizeof(int32_t), s, true)) return -1;
@@ -1703,19 +1742,6 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     if (buf_ensure(e->eef, std::max<int64_t>(ES, 1) * sizeof(uint8_t), s, true)) return -1;
     part_a = prune_lazy_blocks(ES);
     if (buf_ensure(e->lzpart, part_a * sizeof(int64_t), s)) return -1;
-  }
-  if (side) {
-    if (side_stream(e)) return -1;
-    TNP_CHECK(hipEventRecord(e->ev_s2[0], s));
-    TNP_CHECK(hipStreamWaitEvent(e->s2, e->ev_s2[0], 0));
-    const int t = ktimer_begin(e, "prune", 1.0 * E + 36.0 * S, e->s2);
-    if (launch_prune_lazy(P<int32_t>(e->edges), E, P<int32_t>(e->sb), S, V, nullptr, nb, 0, idx, K - 1,
-                          P<uint64_t>(c.pz), P<uint8_t>(e->edm), P<uint8_t>(e->eef), P<uint8_t>(e->live),
-                          P<int64_t>(e->lzpart), ctr, e->s2, 0, ES))
-      return -1;
-    ktimer_end(e, t, e->s2);
-    TNP_CHECK(hipEventRecord(e->ev_s2[1], e->s2));
-    e->s2_pending = true;
   }
   for (int attempt = 0; attempt < 3; ++attempt) {
     if (buf_ensure(e->ckeys_a, std::max<int64_t>(cap, 1) * sizeof(uint64_t), s)) return -1;
@@ -1736,7 +1762,7 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
       // WCELL members) + pair-cell lists and k_connect's chunk table (bcap)
       if (buf_ensure(e->bcell, bcap * sizeof(int32_t), s)) return -1;
       const ConnectWin cw{idx, nb, cfmask, P<uint64_t>(e->ckeys_a), cap, xs, bstat,
-                          e->packed_records && packed_ok(idx, K) ? 1 : 0};
+                          packed_ok(idx, K) ? 1 : 0};
       // the LDS-record path's cell-order scratch (TNP_LDS_RECORDS=0: off)
       const bool lrec = e->lds_records;
       if (lrec && buf_ensure(e->bk[4], TB * sizeof(uint64_t), s)) return -1;  // (entry words or indices)
@@ -1765,53 +1791,14 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     }
     int64_t seq = 0;
     if (post_ctr(e, s, &seq)) return -1;
-    if (early_prune && attempt == 0 && !side) {  // (a redone connect leaves part A as it is)
+    if (early_prune && attempt == 0) {  // (a redone connect leaves part A as it is)
       TIMED("prune", 1.0 * E + 36.0 * S,
             launch_prune_lazy(P<int32_t>(e->edges), E, P<int32_t>(e->sb), S, V, nullptr, nb, 0, idx, K - 1,
                               P<uint64_t>(c.pz), P<uint8_t>(e->edm), P<uint8_t>(e->eef), P<uint8_t>(e->live),
                               P<int64_t>(e->lzpart), ctr, s, 0, ES));
     }
     if (wait_ctr(e, s, seq)) return -1;
-    if (buckets) {
-      // the atomically allocated pair-cell list: cells | pairs << 24
-      e->h_ctr[CTR_R] = e->h_ctr[CTR_PCK] & (PCK_CELLS - 1);
-      e->h_ctr[CTR_TESTS] = e->h_ctr[CTR_PCK] >> 24;
-      if (e->h_ctr[CTR_K0] & 2) {
-        tnp_set_error("plane %d: a vertex outside the mark planes [%d, %d] x [%d, %d] x [%d, %d] the engine "
-                      "was given (tnp_engine_set_span)", idx, sp0[0], sp1[0], sp0[1], sp1[1], sp0[2], sp1[2]);
-        return -1;
-      }
-      if (e->h_ctr[CTR_K0]) {
-        // the reference builds torch.cartesian_prod() of zero tensors (subpoly.py:317)
-        tnp_set_error("meshgrid expects a non-empty TensorList (a region row without zeros, plane %d)",
-                      idx);
-        return -1;
-      }
-      H = e->h_ctr[CTR_H];
-      T = e->h_ctr[CTR_T];
-      // entries: written once by the scatter; the grouping reads them, gathers
-      // 16 B of member keys and writes the 32 B record; the window pass reads
-      // every record (once, algorithmically) and writes the kept keys
-      ktimer_set_bytes(e, "bucket_entries", 16.0 * M + 8.0 * T);
-      if (bg.sub) ktimer_set_bytes(e, "bucket_refine", 24.0 * T);
-      // the window pass re-reads the records the same workgroup just wrote
-      // (cache traffic): its compulsory bytes are the kept keys.  LDS-record
-      // path: 8 B entry word + 16 B member keys + 4 + 4 B cell order (written,
-      // read back) per entry, records in memory only for k_connect's cells
-      // (not counted: an understatement)
-      ktimer_set_bytes(e, "bucket_group", (e->lds_records ? 32.0 : 56.0) * T + 8.0 * e->h_ctr[CTR_XK]);
-    }
-    TT = e->h_ctr[CTR_TESTS];
-    X = e->h_ctr[CTR_XK];
-    ktimer_set_bytes(e, 32.0 * TT + 8.0 * T);  // known only now
-    if (e->h_ctr[CTR_BIG] || TT > e->max_pair_tests) {
-      // one linear region holding ~sqrt(2*tests) vertices: the reference would
-      // materialise every in-region pair (subpoly.py:505-518) and run out of
-      // memory long before; refuse instead of grinding for hours
-      tnp_set_error("degenerate complex at plane %d: %lld in-cell vertex pairs exceed the limit %lld "
-                    "(TNP_MAX_PAIR_TESTS)", idx, (long long)TT, (long long)e->max_pair_tests);
-      return -1;
-    }
+    if (connect_counts(e, f, &TT)) return -1;
     if (e->h_ctr[CTR_BOVF]) {  // chunk table too small: grow, remap, redo
       bcap = connect_chunks(TT) + 1;
       chunks_ok = false;
@@ -1842,10 +1829,22 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     TIMED("pair_sort", 16.0 * X * ((2 * nb + 7) / 8),
           sort_keys_lex(kin, kalt, X, nb, e->sort_run, e->sort_scr.p, e->sort_scr.bytes, &e->ckeys, s));
   }
+  f.part_a = part_a;
+  f.lazy = lazy;
+  return 0;
+}
 
-  // 5. pruning over [edges; e_new; c_new] + vertex compaction (after the side
-  // stream's part A: everything below may move or read the edge slots)
-  side_join(e, s);
+// 5. pruning over [edges; e_new; c_new] + vertex compaction: the lazy prune
+//    (what part A left of it), the compacting prune, the last plane's
+//    compaction behind lazily deleted edges, or the plain concatenation
+static int finish_prune(tnp_engine* e, FinishStep& f, hipStream_t s) {
+  const int idx = f.idx, prune = f.prune, nb = f.nb, part_a = f.part_a, K = e->K;
+  const int64_t V = f.V, E = f.E, S = f.S, NV = f.NV, X = f.X, E_live_in = f.E_live;
+  const bool buckets = f.buckets, lazy = f.lazy;
+  VSet& c = e->cur;
+  int64_t* ctr = P<int64_t>(e->ctr);
+  uint64_t* pos = VP(c, e->kw);
+  uint64_t* zero = VZ(c, e->kw);
   const int64_t N = E + S + X;
   int64_t nt = step_tiles(N);
   if (buf_ensure(e->blk, (nt + 1) * sizeof(int32_t), s)) return -1;
@@ -1862,8 +1861,8 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     if (buf_ensure(e->live, std::max<int64_t>(NV + 4, 16), s)) return -1;  // +4: word atomics
     if (!buckets) TNP_CHECK(hipMemsetAsync(e->live.p, 0, NV, s));  // else zeroed by the bucket count
     // (word-atomic live counting inside the prune measured slower than the
-    // counting pass even at bunny scale: 0.25 vs 0.13 + 0.07 ms per subpoly)
-    const bool count_in_prune = false;
+    // counting pass even at bunny scale: 0.25 vs 0.13 + 0.07 ms per subpoly,
+    // and was removed)
     // the run loop leaves the live counts to the next split's hit workers
     // (not in the kernel-timer pass: the prune's modelled bytes want them)
     BucketGeom bgd{};
@@ -1910,12 +1909,12 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
             launch_prune_lb(eg, E, P<int32_t>(e->sb), S, V, e->ckeys, nb, X, idx, K - 1,
                             P<uint64_t>(c.pz), P<uint8_t>(e->edm), P<uint8_t>(e->eef),
                             P<int32_t>(e->edges_alt), P<uint8_t>(e->edm_alt), P<uint8_t>(e->eef_alt),
-                            P<uint8_t>(e->live), count_in_prune, ctr, lb, s));
+                            P<uint8_t>(e->live), ctr, lb, s));
       std::swap(e->edm, e->edm_alt);
       std::swap(e->eef, e->eef_alt);
       if (defer)
         e->pend_lz_n = 0;  // (E_live: the compacting prune's own count, read back below)
-      else if (!count_in_prune)
+      else
         TIMED("count_live", 1.0 * NV, launch_count_flags(P<uint8_t>(e->live), NV, ctr, CTR_V, s));
     }
     next_valid = (e->keep_all || eps2(e)) ? 0 : std::min(idx + 1, K - 1);
@@ -1942,7 +1941,7 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     if (lb_begin(e, lb_tiles(N), s, &lb, 0, false)) return -1;
     if (launch_prune_lb(eg, E, P<int32_t>(e->sb), S, V, e->ckeys, nb, X, -1, K - 1, P<uint64_t>(c.pz),
                         P<uint8_t>(e->edm), P<uint8_t>(e->eef), P<int32_t>(e->edges_alt),
-                        P<uint8_t>(e->edm_alt), P<uint8_t>(e->eef_alt), P<uint8_t>(e->live), false, ctr, lb, s))
+                        P<uint8_t>(e->edm_alt), P<uint8_t>(e->eef_alt), P<uint8_t>(e->live), ctr, lb, s))
       return -1;
     std::swap(e->edm, e->edm_alt);
     std::swap(e->eef, e->eef_alt);
@@ -1961,35 +1960,83 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
     if (read_ctr(e, s)) return -1;
   }
   if (swap_edges) std::swap(e->edges, e->edges_alt);
+  f.V_out = V2;
+  f.E_out = E2;
+  f.E_live_out = E2_live;
+  f.next_valid = next_valid;
+  f.defer = defer;
+  return 0;
+}
+
+extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override_, void* stream,
+                                 tnp_step_stats* st) {
+  hipStream_t s = (hipStream_t)stream;
+  TNP_CHECK(hipSetDevice(e->device));
+  if (e->pend_idx != idx) { tnp_set_error("finish(%d) without split(%d)", idx, idx); return -1; }
+  if (require_valid(e, "finish")) return -1;
+  if (e->cnt_pending) {  // (the split resolves them; a finish never sees them pending)
+    tnp_set_error("finish(%d): live counts of the last step still pending", idx);
+    return -1;
+  }
+  e->pend_idx = -1;
+  e->valid = false;  // until this step has completed
+  FinishStep f{};
+  f.idx = idx;
+  f.prune = prune;
+  f.override_ = override_;
+  f.hits_done = e->pend_hits;
+  f.hoff = f.hits_done ? e->pend_hoff : -1;
+  e->pend_hits = false;
+  int64_t S_kept = e->pend_S;
+  if (e->curve) {
+    if (curve_filter(e, idx, override_, s, &S_kept)) return -1;
+    e->masks_valid = false;  // the filter rewired the kept split edges
+    // the kept splits another shard owns (read back with the connect
+    // counters; the split's CTR_DUP count is the flat path's)
+    TNP_CHECK(hipMemsetAsync(P<int64_t>(e->ctr) + CTR_DUP, 0, sizeof(int64_t), s));
+    if (launch_count_unowned(P<uint64_t>(e->cur.grid) + e->V, S_kept, e->own, P<int64_t>(e->ctr), s))
+      return -1;
+  }
+  f.V = e->V;
+  f.E = e->E;
+  f.S = S_kept;
+  f.NV = f.V + f.S;
+  f.E_live = e->E_live;
+  f.buckets = uses_buckets(e, &f.bg);
+  f.nb = 1;
+  while (f.nb < 31 && (1ll << f.nb) < f.NV) ++f.nb;
+  if (finish_new_keys(e, f, s) || finish_members(e, f, s)) return -1;
+  if (f.buckets ? finish_buckets(e, f, s) : finish_radix_cells(e, f, s)) return -1;
+  if (finish_connect(e, f, s) || finish_prune(e, f, s)) return -1;
   // the new vertices hold planes >= pend_keep only: valid_from never claims
   // the planes below (a step order that could read them needs keep_all)
-  if (e->pend_fused) next_valid = std::max(next_valid, e->pend_keep);
+  if (e->pend_fused) f.next_valid = std::max(f.next_valid, e->pend_keep);
   const int64_t V_in_live = e->V_live;
-  e->V = NV;  // slots
-  e->V_live = V2;
-  e->E = E2;
-  e->E_live = E2_live;
-  e->valid_from = next_valid;
-  if (defer) {  // V_live (and the lazy prune's E_live) arrive with the next split
+  e->V = f.NV;  // slots
+  e->V_live = f.V_out;
+  e->E = f.E_out;
+  e->E_live = f.E_live_out;
+  e->valid_from = f.next_valid;
+  if (f.defer) {  // V_live (and the lazy prune's E_live) arrive with the next split
     e->cnt_pending = true;
     e->pend_st = st;
   }
   if (st) {
     st->idx = idx;
     st->V_in = V_in_live;
-    st->E_in = E_live_in;
-    st->S = S;
-    st->H = H;
+    st->E_in = f.E_live;
+    st->S = f.S;
+    st->H = f.H;
     st->X = e->h_ctr[CTR_X];  // all connecting edges (X kept ones were appended)
-    st->V_out = V2;
-    st->E_out = E2_live;
+    st->V_out = f.V_out;
+    st->E_out = f.E_live_out;
     st->A = e->h_ctr[CTR_A];
     st->P = e->h_ctr[CTR_P];
     st->pair_tests = (e->h_ctr[CTR_PCK] ? (e->h_ctr[CTR_PCK] >> 24) : e->h_ctr[CTR_TESTS]) + e->h_ctr[CTR_SPAIRS];
     st->override_applied = override_ < 0 ? (e->h_ctr[CTR_FAIL] != 0) : override_;
     st->next_active = (uint64_t)e->h_ctr[CTR_ACTIVE];
     st->S_dup = e->curve ? e->h_ctr[CTR_DUP] : e->pend_dup;
-    st->T = T;
+    st->T = f.T;
   }
   e->valid = true;
   return 0;
@@ -2019,7 +2066,7 @@ extern "C" int tnp_engine_run_steps(tnp_engine* e, void* stream, tnp_step_stats*
     e->pend_st = nullptr;
     return rc;
   };
-  e->defer_counts = e->defer_ok;
+  e->defer_counts = true;
   e->in_run = true;
   e->ctr_zero = false;
   for (int idx = 0; idx < K; ++idx) {

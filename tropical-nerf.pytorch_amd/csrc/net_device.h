@@ -428,12 +428,8 @@ __device__ __forceinline__ void mfma_layer(const float* Wl, const float (&act)[4
 }
 
 // the layers of an NL-layer net that run on MFMA: hidden widths of 16 or 32
-// (TNP_FWD_MFMA=0: variant builds for A/B, every layer on VALU as round 5)
-#ifndef TNP_FWD_MFMA
-#define TNP_FWD_MFMA 1
-#endif
 template <int H>
-__host__ __device__ constexpr bool mfma_shape() { return TNP_FWD_MFMA && H % 16 == 0; }
+__host__ __device__ constexpr bool mfma_shape() { return H % 16 == 0; }
 
 template <int LV, int H, int NL>
 struct NetShape {

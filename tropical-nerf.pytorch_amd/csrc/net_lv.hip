@@ -15,8 +15,6 @@
 // Bitwise contract with the PyTorch-CPU path: net.hip header; every Linear
 // layer follows the MKL schedule of its shape and row count (net_device.h
 // lin_mode / linear_mode).  Compiled with -ffp-contract=off.
-#include <cstdlib>
-
 #include "common.h"
 #include "kernels.h"
 #include "net_device.h"
@@ -113,12 +111,6 @@ k_forward(NetDev net, const float* __restrict__ xyz, int64_t n, float* __restric
 // (a new vertex off one of its shared planes by more than eps) is ORed into
 // ctr[CTR_FAIL]; shared[r] keeps the plane set for k_override_new.  Values
 // and the MKL row-count schedule are those of k_forward (same n = S).
-// EXP (timing experiments only, -DTNP_FWD_SHADOW builds: a shadow launch
-// before the real one, tools/fwd_shadow.py): 1 no stores (a checksum), 2
-// endpoints read coalesced (slots i, i + 1), 4 no zero-key gathers, 8 no
-// plane-value gathers, 16 no coordinate gathers, 32 no encoding; 64: the
-// real kernel (its outputs rewritten by the real launch); 128 the grid word
-// without the marks search (an arithmetic stand-in)
 // k_forward_new's grid: one workgroup per 256 splits (n < 0: the count on
 // the device, -n its bound)
 inline unsigned fwd_new_grid(int64_t n) { return tnp_grid(n >= 0 ? n : -n); }
@@ -138,19 +130,14 @@ __device__ __forceinline__ void key_store_stream(uint64_t* a, int64_t v, const K
 #pragma unroll
   for (int q = 0; q < KW; ++q) __builtin_nontemporal_store(k.w[q], &a[KW * v + q]);
 }
-#ifndef TNP_FWD_MINB  // workgroups per CU the register budget is cut for (4: 100 VGPRs, no spill)
-#define TNP_FWD_MINB 4
-#endif
-template <int LV, int H, int NL, int EXP = 0>
-__global__ void __launch_bounds__(TNP_BLOCK, TNP_FWD_MINB)
+// 4: workgroups per CU the register budget is cut for (100 VGPRs, no spill)
+template <int LV, int H, int NL>
+__global__ void __launch_bounds__(TNP_BLOCK, 4)
 k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ pre,
               int64_t ld, int64_t V, int keep_from, const int32_t* __restrict__ sa,
               const int32_t* __restrict__ sb, int idx, OwnBox own, uint64_t* pos,
               uint64_t* zero, uint64_t* __restrict__ grid, uint64_t* __restrict__ shared,
-              int64_t* __restrict__ ctr, uint64_t* pz, const float* __restrict__ scol,
-              uint32_t* __restrict__ sink = nullptr) {
-  constexpr bool NOST = (EXP & 1) != 0;
-  uint32_t chk = 0;
+              int64_t* __restrict__ ctr, uint64_t* pz, const float* __restrict__ scol) {
   constexpr int IN = 2 * LV;
   constexpr int NW = NetShape<LV, H, NL>::NW;
   constexpr int KW = key_words((NL - 1) * H + 1);
@@ -173,7 +160,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
   __shared__ float w[NW];
   __shared__ float mk[TNP_MAX_MARKS];
   // MFMA path: each wave's LDS stage for the row <-> lane-layout transposes
-  __shared__ float stg[(EXP == 0 && mfma_shape<H>()) ? TNP_WAVES * 16 * MST : 1];
+  __shared__ float stg[mfma_shape<H>() ? TNP_WAVES * 16 * MST : 1];
   for (int i = threadIdx.x; i < NW; i += blockDim.x) w[i] = net.weights[i];
   for (int i = threadIdx.x; i < net.n_marks; i += blockDim.x) mk[i] = net.marks[i];
   __syncthreads();
@@ -185,24 +172,20 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
   Key<KW> m = tnp::key_zero<KW>();
   if (live) {
     int a = sa[i], b = sb[i];
-    if constexpr ((EXP & 2) != 0) {
-      a = (int)min<int64_t>(i, V - 1);
-      b = (int)min<int64_t>(i + 1, V - 1);
-    }
     // every gather the endpoints need, issued before the first store (the
     // coordinate store could alias zero[] for the compiler)
-    const Key<KW> za = (EXP & 4) ? tnp::key_zero<KW>() : tnp::vkey_load<KW>(zero, a);
-    const Key<KW> zb = (EXP & 4) ? tnp::key_zero<KW>() : tnp::vkey_load<KW>(zero, b);
+    const Key<KW> za = tnp::vkey_load<KW>(zero, a);
+    const Key<KW> zb = tnp::vkey_load<KW>(zero, b);
     if (scol) {
       // the split point itself (k_new_vertices, subpoly.py:113-117, 180), fused:
       // d = d/eps; w = |d0| / |d1 - d0|; v = e0*(1-w) + e1*w
       const float* base = xyz - 3 * V;  // xyz points at slot V
-      const float c0 = (EXP & 8) ? 1.0f : scol[a], c1 = (EXP & 8) ? -1.0f - (float)(i & 7) : scol[b];
+      const float c0 = scol[a], c1 = scol[b];
       float ea[3], eb[3];
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
-        ea[d] = (EXP & 16) ? (float)(i & 255) * 0.003f : base[3 * (int64_t)a + d];
-        eb[d] = (EXP & 16) ? (float)(i & 127) * 0.002f : base[3 * (int64_t)b + d];
+        ea[d] = base[3 * (int64_t)a + d];
+        eb[d] = base[3 * (int64_t)b + d];
       }
       const float d0 = __fdiv_rn(c0, eps_s), d1 = __fdiv_rn(c1, eps_s);
       const float w = __fdiv_rn(fabsf(d0), fabsf(__fsub_rn(d1, d0)));
@@ -211,8 +194,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
 #pragma unroll
       for (int d = 0; d < 3; ++d) {
         const float v = __fadd_rn(__fmul_rn(ea[d], om), __fmul_rn(eb[d], w));
-        if constexpr (NOST) chk ^= __float_as_uint(v);
-        else st_stream(out[d], v);
+        st_stream(out[d], v);
         x[d] = __fmul_rn(__fadd_rn(v, 1.0f), 0.5f);  // Net.preprocess, as load_point (x/2 == x*0.5 exactly)
       }
     } else {
@@ -222,12 +204,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
   }
   float h[H > IN ? H : IN];
   float a[H];
-  if constexpr ((EXP & 32) != 0) {
-#pragma unroll
-    for (int q = 0; q < IN; ++q) h[q] = x[q % 3] * (float)(q + 1);
-  } else {
-    encode<LV>(net, x, h);
-  }
+  encode<LV>(net, x, h);
   const float* W = w;
   int p = 0;
   Key<KW> ps = tnp::key_zero<KW>(), zs = tnp::key_zero<KW>();
@@ -242,7 +219,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
     bad |= tnp::key_test(m, pp) && fabsf(v) > eps_s;
   };
   bool on_mfma = false;
-  if constexpr (EXP == 0 && mfma_shape<H>()) {
+  if constexpr (mfma_shape<H>()) {
     // >= 16 rows: every hidden layer is the SEQ schedule (lin_mode) -> MFMA
     // (net_device.h mfma_layer); the wave's rows go through LDS twice per 16
     // planes: features in, pre-activations back out to one row per lane
@@ -298,10 +275,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
       }
     }
   }
-#ifndef TNP_FWD_VALU_PATH  // 0: timing experiments only (tools/build_lv_variant.sh): no VALU layers
-#define TNP_FWD_VALU_PATH 1  // on MFMA shapes, so < 16-row batches compute nothing
-#endif
-  if (!on_mfma && (TNP_FWD_VALU_PATH || !mfma_shape<H>() || EXP != 0)) {
+  if (!on_mfma) {
     // VALU: the small-batch schedules (ONE / FOLD, < 16 rows), 8-wide nets
 #pragma unroll
     for (int layer = 0; layer < NL - 1; ++layer) {
@@ -315,13 +289,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
 #pragma unroll
       for (int j = 0; j < H; ++j) {
         const float v = a[j];
-        if constexpr (NOST) chk ^= __float_as_uint(v);
-        else plane(p + j, v);
-        if constexpr (NOST) {
-          tnp::key_put(ps, p + j, v > eps);
-          tnp::key_put(zs, p + j, fabsf(v) <= eps);
-          bad |= tnp::key_test(m, p + j) && fabsf(v) > eps_s;
-        }
+        plane(p + j, v);
         h[j] = fmaxf(v, 0.0f);
       }
       p += H;
@@ -332,16 +300,6 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
   float o[2];
   linear_mode<H, 2>(W, W + 2 * H, h, o, mo, i);
   const float v = __fsub_rn(o[1], o[0]);
-  if (NOST) {
-    tnp::key_put(ps, p, v > eps);
-    tnp::key_put(zs, p, fabsf(v) <= eps);
-    bad |= tnp::key_test(m, p) && fabsf(v) > eps_s;
-    chk ^= __float_as_uint(v) ^ (uint32_t)tnp::key_pop(ps) ^ ((uint32_t)tnp::key_pop(zs) << 8) ^ (uint32_t)bad;
-    const uint64_t g = grid_word(mk, net.n_marks, eps, x);
-    chk ^= (uint32_t)g ^ (uint32_t)(g >> 32);
-    if (chk == 0x9E3779B9u && i == 0x7FFFFFFF) sink[0] = chk;  // never: keeps the work
-    return;
-  }
   if (live) {
     if (p >= keep_from) st_stream(col[(int64_t)p * ld], v);
     tnp::key_put(ps, p, v > eps);
@@ -353,10 +311,7 @@ k_forward_new(NetDev net, const float* xyz, int64_t n_arg, float* __restrict__ p
   // full lower_bound over the marks in LDS: cheaper than gathering the
   // endpoints' grid words to narrow it (measured at 128^3: 1.02 -> 0.90 ms
   // per pass for this kernel)
-  // (EXP & 128: timing experiment -- an arithmetic stand-in for the marks search)
-  const uint64_t g = (EXP & 128) ? (uint64_t)(uint32_t)(int)(x[0] * 127.f) | ((uint64_t)(uint32_t)(int)(x[1] * 127.f) << 16) |
-                                       ((uint64_t)(uint32_t)(int)(x[2] * 127.f) << 32)
-                                 : grid_word(mk, net.n_marks, eps, x);
+  const uint64_t g = grid_word(mk, net.n_marks, eps, x);
   if (live) grid[V + i] = g;
   // a shard's failover predicate covers the new vertices it owns: their OR
   // over the shards is the whole batch's, while a halo vertex is another
@@ -480,49 +435,7 @@ int lv_forward_new<LVC>(const NetDev& net, const float* xyz, int64_t n, float* p
                         int keep_from, const int32_t* sa, const int32_t* sb, int idx, const OwnBox& own,
                         uint64_t* pos, uint64_t* zero, uint64_t* grid, uint64_t* shared, int64_t* ctr, uint64_t* pz,
                         const float* col, hipStream_t s) {
-#ifdef TNP_FWD_SHADOW
-  // the shadow launch's own time (HIP events; it runs first, on the caches the
-  // real launch would see), summed over the process and printed at exit
-  static const int shadow = getenv("TNP_FWD_SHADOW") ? atoi(getenv("TNP_FWD_SHADOW")) : 0;
-  static uint32_t* sink = nullptr;
-  static hipEvent_t ev[2];
-  static bool pending = false;
-  static double total_ms = 0.0;
-  static int64_t launches = 0;
-  if (shadow && !sink) {
-    (void)hipMalloc(&sink, 64);
-    (void)hipEventCreate(&ev[0]);
-    (void)hipEventCreate(&ev[1]);
-    atexit([] { fprintf(stderr, "fwd_shadow mode %d: %.4f ms over %lld launches\n", shadow, total_ms, (long long)launches); });
-  }
-  if (pending) {
-    float ms = 0.f;
-    (void)hipEventSynchronize(ev[1]);
-    (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
-    total_ms += ms;
-    ++launches;
-    pending = false;
-  }
-  if (shadow) (void)hipEventRecord(ev[0], s);
-#define TNP_SHADOW(M)                                                                                          \
-  case M:                                                                                                      \
-    hipLaunchKernelGGL((k_forward_new<LVC, H, NL, M>), dim3(fwd_new_grid(n)), dim3(TNP_BLOCK), 0, s, net, xyz, n, pre, \
-                       ld, V, keep_from, sa, sb, idx, own, pos, zero, grid, shared, ctr, pz, col, sink);       \
-    break;
-#define TNP_SHADOW_LAUNCH                                                                                      \
-  switch (shadow) {                                                                                            \
-    TNP_SHADOW(1) TNP_SHADOW(3) TNP_SHADOW(5) TNP_SHADOW(9) TNP_SHADOW(17) TNP_SHADOW(33) TNP_SHADOW(29)       \
-    TNP_SHADOW(61) TNP_SHADOW(64) TNP_SHADOW(192) default: break;                                              \
-  }                                                                                                            \
-  if (shadow) {                                                                                                \
-    (void)hipEventRecord(ev[1], s);                                                                            \
-    pending = true;                                                                                            \
-  }
-#else
-#define TNP_SHADOW_LAUNCH
-#endif
 #define TNP_SHAPE_BODY                                                                                   \
-  TNP_SHADOW_LAUNCH                                                                                      \
   hipLaunchKernelGGL((k_forward_new<LVC, H, NL>), dim3(fwd_new_grid(n)), dim3(TNP_BLOCK), 0, s, net, xyz, n, pre, ld, \
                      V, keep_from, sa, sb, idx, own, pos, zero, grid, shared, ctr, pz, col);
   TNP_SHAPE_SWITCH_ALL(net)

@@ -1001,8 +1001,8 @@ __global__ void __launch_bounds__(TNP_BLOCK, 4)
 k_prune_lb(EdgeSrc src, int64_t N, int64_t ntiles, int idx, Key<KW> amask,
            const uint64_t* __restrict__ pz, const uint8_t* __restrict__ dm,
            const uint8_t* __restrict__ ef, int32_t* __restrict__ out, uint8_t* __restrict__ odm,
-           uint8_t* __restrict__ oef, uint8_t* __restrict__ used, int count_live,
-           int64_t* __restrict__ ctr, TnpLB lb) {
+           uint8_t* __restrict__ oef, uint8_t* __restrict__ used, int64_t* __restrict__ ctr,
+           TnpLB lb) {
   __shared__ int cnt[LIPT][TNP_WAVES];
   __shared__ int64_t slot;
   __shared__ uint64_t acts[TNP_WAVES];
@@ -1100,7 +1100,6 @@ k_prune_lb(EdgeSrc src, int64_t N, int64_t ntiles, int idx, Key<KW> amask,
   // (its tiles publish tens of µs after dispatch: poll long before recomputing)
   const int64_t prefix = tnp::lb_prefix_rc(lb, tile, agg, &slot, tile_agg, TNP_PRUNE_SPIN);
   int64_t run = prefix;
-  int newly = 0;  // count_live: endpoints this thread marked live first
 #pragma unroll
   for (int k = 0; k < LIPT; ++k) {
     int64_t off = run;
@@ -1118,26 +1117,10 @@ k_prune_lb(EdgeSrc src, int64_t N, int64_t ntiles, int idx, Key<KW> amask,
                                   reinterpret_cast<uint64_t*>(out) + o);  // (int2 {a, b})
       odm[o] = (uint8_t)d[k];
       oef[o] = (uint8_t)m[k];
-      if (count_live) {
-        // small complexes: the distinct live count without a counting pass
-        // (a word-wide atomic OR tells who set each byte first)
-        unsigned* w4 = reinterpret_cast<unsigned*>(used);
-        const int ab[2] = {a[k], b[k]};
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-          const unsigned sh = 8u * (unsigned)(ab[q] & 3);
-          newly += ((atomicOr(w4 + (ab[q] >> 2), 1u << sh) >> sh) & 0xFFu) == 0u;
-        }
-      } else {
-        used[a[k]] = 1;
-        used[b[k]] = 1;
-      }
+      used[a[k]] = 1;
+      used[b[k]] = 1;
     }
     run += tot;
-  }
-  if (count_live) {
-    const int wn = tnp::wave_sum(newly);
-    if (tnp::lane() == 0 && wn) atomicAdd((unsigned long long*)&ctr[CTR_V], (unsigned long long)wn);
   }
   if (tile == ntiles - 1 && threadIdx.x == 0) ctr[CTR_E] = prefix + agg;
   act = tnp::wave_or(act);
@@ -1699,8 +1682,8 @@ int launch_prune(bool emit, const int32_t* edges, int64_t E, const int32_t* sb, 
 int launch_prune_lb(const int32_t* edges, int64_t E, const int32_t* sb, int64_t S, int64_t V,
                     const uint64_t* ckeys, int nb, int64_t X, int idx, int last_plane,
                     const uint64_t* pz, const uint8_t* dm, const uint8_t* ef, int32_t* out,
-                    uint8_t* odm, uint8_t* oef, uint8_t* used, bool count_live, int64_t* ctr,
-                    const TnpLB& lb, hipStream_t s) {
+                    uint8_t* odm, uint8_t* oef, uint8_t* used, int64_t* ctr, const TnpLB& lb,
+                    hipStream_t s) {
   EdgeSrc src{edges, E, sb, S, V, ckeys, nb, X};
   const int64_t N = E + S + X;
   if (N <= 0) {
@@ -1710,22 +1693,15 @@ int launch_prune_lb(const int32_t* edges, int64_t E, const int32_t* sb, int64_t 
   const int64_t tiles = lb_tiles(N);
   if (kw_of(last_plane) == 2)
     hipLaunchKernelGGL(k_prune_lb<2>, dim3((unsigned)tiles), dim3(TNP_BLOCK), 0, s, src, N, tiles, idx,
-                       plane_mask<2>(idx + 1, last_plane), pz, dm, ef, out, odm, oef, used, count_live ? 1 : 0, ctr,
-                       lb);
+                       plane_mask<2>(idx + 1, last_plane), pz, dm, ef, out, odm, oef, used, ctr, lb);
   else
     hipLaunchKernelGGL(k_prune_lb<1>, dim3((unsigned)tiles), dim3(TNP_BLOCK), 0, s, src, N, tiles, idx,
-                       plane_mask<1>(idx + 1, last_plane), pz, dm, ef, out, odm, oef, used, count_live ? 1 : 0, ctr,
-                       lb);
+                       plane_mask<1>(idx + 1, last_plane), pz, dm, ef, out, odm, oef, used, ctr, lb);
   TNP_CHECK(hipGetLastError());
   return 0;
 }
 int prune_lazy_blocks(int64_t N) {
-  static const int64_t s_max = [] {  // TNP_PL_BLOCKS: the grid cap (experiments)
-    const char* v = getenv("TNP_PL_BLOCKS");
-    const int64_t b = v ? atoll(v) : PRUNE_LAZY_MAX_BLOCKS;
-    return b > 0 ? b : (int64_t)PRUNE_LAZY_MAX_BLOCKS;
-  }();
-  return (int)std::max<int64_t>(1, std::min<int64_t>(s_max, (N + TNP_BLOCK * LZ_IPT - 1) / (TNP_BLOCK * LZ_IPT)));
+  return (int)std::max<int64_t>(1, std::min<int64_t>(PRUNE_LAZY_MAX_BLOCKS, (N + TNP_BLOCK * LZ_IPT - 1) / (TNP_BLOCK * LZ_IPT)));
 }
 int launch_prune_lazy(int32_t* edges, int64_t E, const int32_t* sb, int64_t S, int64_t V, const uint64_t* ckeys,
                       int nb, int64_t X, int idx, int last_plane, const uint64_t* pz, uint8_t* dm, uint8_t* ef,
