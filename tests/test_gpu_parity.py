@@ -310,11 +310,13 @@ def test_lookback_recompute_path(cuda):
 
 @pytest.mark.parametrize("name", ["synth32", "synth64h"])
 def test_lds_record_path(cuda, name):
-    """The grouping kernel keeps the records of buckets above one chunk in
-    LDS (csrc/bucket.hip k_bucket_group: cell order in memory, 192-position
-    chunks gathered three deep); every step state must be bitwise the same
+    """The grouping kernel keeps the records of buckets above 256 entries out
+    of memory (csrc/bucket.hip wave_windows: the entry words in cell order in
+    memory, each wave building its windows' records in a private 64-record
+    LDS stage, pipelined two deep); every step state must be bitwise the same
     with the path off (records through memory) and equal to the reference's
-    step records (synth64h: buckets of thousands of entries, many chunks)."""
+    step records (synth64h: buckets of thousands of entries, many windows
+    per wave)."""
     from tropical._engine import engine_for
     d = load(name)
     net = product_net(d, cuda)

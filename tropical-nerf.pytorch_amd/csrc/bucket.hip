@@ -55,24 +55,9 @@ __device__ __forceinline__ int member_of(const int32_t* members, int64_t S, int6
 
 using BGeom = BucketGeom;
 
-// the window pass the grouping kernel runs over each bucket (keys == null:
-// none; the engine then launches k_connect_win)
-struct WinArgs {
-  int idx, nb;
-  uint64_t fmask;
-  uint64_t* keys;
-  int64_t cap;
-  int64_t* xs;  // per-XCD shards of the appends and pair statistics (step.h); null: ctr
-  // small grids (no shards): per-bucket pair statistics [NB][4] (compatible
-  // pairs, shared regions, connecting edges, window-pass pairs), plain
-  // stores that k_connect's first workgroup sums -- instead of 4 atomics per
-  // bucket on the counter block's words (~11 ns each, serialised)
-  int64_t* bstat;
-  int packed;  // the LDS-record path stages packed records (connect.h packed_ok)
-};
-
 // a bucket's pair statistics -> its bstat row, or the counter block / shards
-__device__ __forceinline__ void bucket_stats_out(const WinArgs& wa, int b, int64_t c, int64_t g, int64_t x,
+// (wa: the window pass the grouping kernel runs over each bucket, step.h)
+__device__ __forceinline__ void bucket_stats_out(const ConnectWin& wa, int b, int64_t c, int64_t g, int64_t x,
                                                  int64_t sp, int64_t* __restrict__ ctr) {
   if (wa.bstat) {
     int64_t* r = wa.bstat + 4 * (int64_t)b;
@@ -95,7 +80,7 @@ struct PairLists {
   int32_t* bcell;
   int64_t bcap, chunk;
   int32_t *bcount, *bcur;
-  int32_t* perm;  // LDS-record path: every bucket's entries in cell order (entry indices; null: off)
+  uint64_t* cell_words;  // LDS-record path: every bucket's entry words in cell order (null: off)
 };
 
 // the new vertices' failover override, applied by the bucket count
@@ -639,13 +624,23 @@ k_bucket_refine(int NB, const int64_t* __restrict__ bbase, const uint64_t* __res
 #define TNP_GIPT 8
 #endif
 constexpr int GIPT = TNP_GIPT;
-// SW: the grouping writes the bucket's entry words in cell order (8 B per
-// entry) for the LDS-record pass, one dependent gather less than the entry
-// indices (4 B)
-#ifndef TNP_SORTED_WORDS
-#define TNP_SORTED_WORDS 1
-#endif
-constexpr bool SW = TNP_SORTED_WORDS;
+// group buckets are 8^3 cells in every geometry (bucket_geometry: the member
+// passes' own buckets, or the octants of their 16^3-cell ones)
+constexpr int SH = 3;
+constexpr int LC = 1 << (3 * SH);  // cells of a group bucket
+
+// an entry's pair-test record: its entry word (local cell << 40 | cell flags
+// << 32 | vertex), the member's (pos, zero) keys and the cell's tag
+__device__ __forceinline__ CellEnt make_record(uint64_t w, const ulonglong2& k, uint32_t tag) {
+  CellEnt r;
+  r.p = k.x;
+  r.z = k.y;
+  r.v = (int32_t)(uint32_t)w;
+  r.f = (uint32_t)(w >> 32) & 63u;
+  r.tag = tag;
+  r.pad = 0;
+  return r;
+}
 
 // pair cell o of the global list (cell id, first entry, m members, first
 // pair lo) and its chunks in k_connect's chunk table
@@ -678,14 +673,12 @@ __device__ __forceinline__ void group_origin(const BGeom& G, int b, int& ox, int
 }
 
 // the grouping of one bucket of n >= 2 entries (k_bucket_group)
-template <int SH>
 __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base, int64_t n,
                                              const uint64_t* __restrict__ ekv,
                                              const ulonglong2* __restrict__ pz, CellEnt* __restrict__ ents,
                                              const PairLists& pl, int64_t* __restrict__ ctr, int* cnt,
                                              int* cur, int64_t* lds, int64_t* lds3, int64_t* s_pk,
-                                             int64_t* s_sp, void* order) {
-  constexpr int LC = 1 << (3 * SH);
+                                             int64_t* s_sp, uint64_t* order) {
   for (int i = threadIdx.x; i < LC; i += TNP_BLOCK) cnt[i] = 0;
   __syncthreads();
   const uint64_t* kv = ekv + base;
@@ -714,9 +707,9 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
   }
   __syncthreads();
   // records, cell-contiguous: the member keys gathered here (the members of
-  // one bucket are spatially close: their slots cluster).  perm != null
-  // (the LDS-record path): the entries' cell order goes to perm[] instead,
-  // records are written only for the cells k_connect takes
+  // one bucket are spatially close: their slots cluster).  order != null
+  // (the LDS-record path): the entry words go to order[] in cell order
+  // instead, records are written only for the cells k_connect takes
   for (int64_t e0 = 0; e0 < n; e0 += TNP_BLOCK * GIPT) {
     uint64_t w[GIPT];
     int pos[GIPT];
@@ -737,22 +730,13 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
       if (w[k] == ~0ull) continue;
       const int lc = (int)(w[k] >> 40);
       if (order) {
-        if (SW)
-          static_cast<uint64_t*>(order)[pos[k]] = w[k];
-        else
-          static_cast<int32_t*>(order)[pos[k]] = (int32_t)(e0 + k * TNP_BLOCK + threadIdx.x);
+        order[pos[k]] = w[k];
         if (cnt[lc] <= WCELL) continue;
       }
-      CellEnt r;
-      r.p = k2[k].x;
-      r.z = k2[k].y;
-      r.v = (int32_t)(uint32_t)w[k];
-      r.f = (uint32_t)(w[k] >> 32) & 63u;
       // the cell's tag for the window pass; cells above WCELL members are
       // flagged: the flattened pair-space pass (k_connect) takes them
-      r.tag = ((uint32_t)b * (uint32_t)LC + (uint32_t)lc) | (cnt[lc] > WCELL ? 0x80000000u : 0u);
-      r.pad = 0;
-      ents[base + pos[k]] = r;
+      ents[base + pos[k]] = make_record(
+          w[k], k2[k], ((uint32_t)b * (uint32_t)LC + (uint32_t)lc) | (cnt[lc] > WCELL ? 0x80000000u : 0u));
     }
   }
   __syncthreads();
@@ -840,7 +824,6 @@ __device__ __forceinline__ void group_bucket(const BGeom& G, int b, int64_t base
 // end << 16, bucket-relative) overwrites cnt[0..nwin) -- a window is
 // written only after every count it could overwrite was read.  Returns the
 // window count (valid in lane 0).  n must be < 65536.
-template <int LC>
 __device__ __forceinline__ int build_windows(int* cnt, const int* cur) {
   const int L = tnp::lane();
   int nwin = 0;
@@ -938,7 +921,6 @@ __device__ __forceinline__ int build_windows_range(int* cnt, const int* cur, int
 
 // the first cell whose records start at or after offset `target` (cells in
 // local order; starts non-decreasing): a wave's share of the bucket
-template <int LC>
 __device__ __forceinline__ int first_cell_from(const int* cnt, const int* cur, int target) {
   int lo = 0, hi = LC;
   while (lo < hi) {
@@ -956,14 +938,10 @@ __device__ __forceinline__ int first_cell_from(const int* cnt, const int* cur, i
 // cell-contiguous in the window's LDS slot), and every same-cell pair --
 // also of a cell above WCELL members, at most 64 * 63 / 2 tests -- is tested
 // once by window_tests; the bucket lists no pair cell for k_connect.
-#ifndef TNP_SMALL_BUCKET
-#define TNP_SMALL_BUCKET 1
-#endif
-template <int SH>
 __device__ __forceinline__ void group_small(int b, int64_t base, int n, const uint64_t* __restrict__ ekv,
-                                            const ulonglong2* __restrict__ pz, const WinArgs& wa, uint64_t below,
+                                            const ulonglong2* __restrict__ pz, const ConnectWin& wa,
                                             int64_t* __restrict__ ctr, WinLds& W) {
-  constexpr int LC = 1 << (3 * SH);
+  const uint64_t below = (wa.idx >= 64) ? ~0ull : ((1ull << wa.idx) - 1ull);
   const int L = tnp::lane();
   const bool valid = L < n;
   const uint64_t w = valid ? ekv[base + L] : 0ull;
@@ -972,15 +950,10 @@ __device__ __forceinline__ void group_small(int b, int64_t base, int n, const ui
   const uint32_t key = (lc << 6) | (uint32_t)L;
   int rank = 0;
   for (int q = 0; q < 64; ++q) rank += (uint32_t)__builtin_amdgcn_readlane((int)key, q) < key;
-  CellEnt r;
-  r.p = valid ? k.x : 0ull;
-  r.z = valid ? k.y : 0ull;
-  r.v = valid ? (int32_t)(uint32_t)w : 0;
-  r.f = valid ? ((uint32_t)(w >> 32) & 63u) : 0u;
-  r.tag = valid ? (uint32_t)b * (uint32_t)LC + lc : 0xFFFFFFFFu;  // invalid: matches nothing
-  r.pad = 0;
+  // (an invalid lane's record is all zero -- its w is -- under a tag that matches nothing)
   const int wv = tnp::wave();
-  W.st[wv][rank] = r;
+  W.st[wv][rank] = make_record(w, valid ? k : make_ulonglong2(0ull, 0ull),
+                               valid ? (uint32_t)b * (uint32_t)LC + lc : 0xFFFFFFFFu);
   lds_fence();
   // lane L now takes position L of the window
   const uint32_t tag = W.st[wv][L].tag;
@@ -998,7 +971,7 @@ __device__ __forceinline__ void group_small(int b, int64_t base, int n, const ui
   if (L == 0) bucket_stats_out(wa, b, c, g, x, pairs, ctr);
 }
 
-// The same windows built by the whole workgroup (sh = 3).  The greedy
+// The same windows built by the whole workgroup.  The greedy
 // packing is a chain c0 -> J(c0) -> ... over window-opening cells: a window
 // opened at cell c closes before the first non-empty cell after c that is
 // big or ends beyond s_c + 64 (a binary search over the cells' end
@@ -1007,17 +980,16 @@ __device__ __forceinline__ void group_small(int b, int64_t base, int n, const ui
 // chain is enumerated by pointer doubling (J^(2^k) tables) -- the serial
 // walk of one wave (build_windows) was ~26 % of the grouping kernel's
 // workgroup time at 128^3.  Bit for bit the windows of build_windows.
-// scratch: (NJ + 3) * (LC + 1) uint16 + 8 int of LDS not otherwise in use.
-#ifndef TNP_PAR_WIN
-#define TNP_PAR_WIN 1
-#endif
+// scratch: (NJ + 3) * (LC + 1) uint16 + 8 int of LDS not otherwise in use
+// (the window pass's own WinLds, idle until the pass).
 constexpr int PW_NJ = 10;  // J^(2^k), k < PW_NJ: chains of up to 1024 windows
 // below this many entries the serial walk is shorter than the builder's
 // fixed ~40 barrier-separated steps (bunny-scale buckets hold ~100)
 constexpr int PW_MIN = 512;
-template <int LC>
 __device__ __forceinline__ int build_windows_par(int* cnt, const int* cur, uint16_t* scratch) {
   static_assert(LC + 1 <= 65535 && LC <= (1 << PW_NJ), "cell indices in 16 bits, chains in the tables");
+  static_assert(sizeof(WinLds) >= (PW_NJ + 3) * (LC + 1) * sizeof(uint16_t) + 12 * sizeof(int),
+                "window-builder scratch");
   constexpr int W1 = LC + 1;  // cell index LC: none
   uint16_t* opn = scratch;    // first non-empty cell of <= WCELL members at or after c
   uint16_t* nbg = opn + W1;   // first big cell at or after c
@@ -1128,53 +1100,139 @@ __device__ __forceinline__ int build_windows_par(int* cnt, const int* cur, uint1
   return nw;
 }
 
-// 8^3-cell buckets: 5 workgroups per CU (LDS allows 5; the LDS-record
-// path's pipeline registers would otherwise cost one: 105 VGPRs -> 4 waves
-// per SIMD, bucket_group 0.92 vs 1.04 ms per 128^3 pass at 5)
+// 5 workgroups per CU (LDS allows 5; the LDS-record path's pipeline
+// registers would otherwise cost one: 105 VGPRs -> 4 waves per SIMD,
+// bucket_group 0.92 vs 1.04 ms per 128^3 pass at 5)
 #ifndef TNP_BG_MINB
 #define TNP_BG_MINB 5
 #endif
-#ifndef TNP_PACKED_WIN  // 0: the 32-stride window pass (A/B variant)
-#define TNP_PACKED_WIN 1
-#endif
-// LDS-record path (pl.perm != null): a bucket's records never go through
-// memory -- its cell order goes to pl.perm (4 B per entry), chunks of
-// TNP_LREC_CH record positions (+ 64 for the windows that start near a
-// chunk's end) are gathered into LDS (over the window stage and behind it)
-// and the windows starting in the chunk are tested there.  Only the cells
-// above WCELL members (k_connect's) get records in memory.
-#ifndef TNP_BG_WAVEWIN  // 1: per-wave windows (no workgroup barriers in the pass); 0: shared chunks
-#define TNP_BG_WAVEWIN 1
-#endif
-#ifndef TNP_BG_LDS_MIN  // buckets above this many entries skip the records in memory
+// LDS-record path (pl.cell_words != null): buckets above this many entries
+// keep their records out of memory -- the grouping writes their entry words
+// in cell order to pl.cell_words (8 B per entry) and every wave builds the
+// records of its windows in LDS from those and the member keys
+// (wave_windows).  Only the cells above WCELL members (k_connect's) get
+// records in memory.  (A smaller bucket gains nothing from it: bunny scale)
+constexpr int LREC_N = 256;
+#ifndef TNP_BG_LDS_MIN
 #define TNP_BG_LDS_MIN LREC_N
 #endif
-#ifndef TNP_LREC_CH
-#define TNP_LREC_CH 192  // (256 records: the window stage's own LDS, occupancy unchanged)
-#endif
-constexpr int LREC_N = TNP_LREC_CH + 64;
-constexpr size_t WL_ST = offsetof(WinLds, st);
-constexpr size_t WL_RAW = WL_ST + (sizeof(WinLds) - WL_ST > LREC_N * sizeof(CellEnt) ? sizeof(WinLds) - WL_ST
-                                                                                     : LREC_N * sizeof(CellEnt));
-constexpr int LREC_R = (LREC_N + TNP_BLOCK - 1) / TNP_BLOCK;  // records per thread per chunk
 
+// The window pass of a bucket on the LDS-record path (sw: its n < 65536
+// entry words in cell order; cnt / cur: group_bucket's cell counts and end
+// offsets).  Each wave takes the cells whose records start in its quarter of
+// the bucket, packs them into windows of whole cells itself (the serial walk
+// of build_windows over a quarter of the cells) and walks its windows
+// through a private 64-record stage in LDS: no workgroup barrier from the
+// grouping to the statistics.  A window's records are built from the entry
+// words and the member keys, software-pipelined (the keys of the next window
+// and the words of the one after are in flight while a window is tested).
 // PK: packed records (steps with packed_ok)
-template <int SH, bool PK>
-__global__ void __launch_bounds__(TNP_BLOCK, SH == 3 ? TNP_BG_MINB : 1)
+template <bool PK>
+__device__ __forceinline__ void wave_windows(int b, int64_t n, const uint64_t* sw,
+                                             const ulonglong2* __restrict__ pz, const ConnectWin& wa,
+                                             uint64_t below, int64_t* __restrict__ ctr, int* cnt, const int* cur,
+                                             WinLds& W, WinAcc& a) {
+  const int L = tnp::lane(), wv = tnp::wave();
+  const int nn = (int)n;
+  const int c_lo = wv == 0 ? 0 : first_cell_from(cnt, cur, (int)((int64_t)nn * wv / TNP_WAVES));
+  const int c_hi = wv == TNP_WAVES - 1 ? LC : first_cell_from(cnt, cur, (int)((int64_t)nn * (wv + 1) / TNP_WAVES));
+  // (every wave has read the cells it bounds by before any list is written)
+  __syncthreads();
+  const int nw = uniform(build_windows_range(cnt, cur, c_lo, c_hi));
+  const uint32_t* wl = reinterpret_cast<const uint32_t*>(cnt) + c_lo;
+  auto span = [&](int k, int& s, int& m) {
+    if (k >= nw) { s = 0; m = 0; return; }
+    const uint32_t se = (uint32_t)uniform((int)wl[k]);
+    s = (int)(se & 0xFFFFu);
+    m = (int)(se >> 16) - s;
+  };
+  int s0, m0, s1, m1;
+  span(0, s0, m0);
+  span(1, s1, m1);
+  uint64_t w0 = L < m0 ? sw[s0 + L] : 0ull;
+  uint64_t w1 = L < m1 ? sw[s1 + L] : 0ull;
+  ulonglong2 k0 = L < m0 ? pz[(uint32_t)w0] : make_ulonglong2(0ull, 0ull);
+  // this wave's packed stage (64 records), laid over its W.st slots
+  uint64_t* const ptw = reinterpret_cast<uint64_t*>(&W.st[wv][0]);
+  uint64_t* const paw = ptw + 64;
+  uint32_t* const pvv = reinterpret_cast<uint32_t*>(paw + 64);
+  static_assert(64 * (8 + 8 + 4) <= sizeof(W.st[0]), "a wave's packed stage fits its record slots");
+  const PackedRecs PR{ptw, paw, pvv};
+  uint64_t amask = 0;
+  if (PK && wa.fmask) {
+    const uint64_t lo = (uint32_t)(wa.fmask >> wa.idx);
+    amask = lo | (lo << 32);
+  }
+  for (int k = 0; k < nw; ++k) {
+    // in flight behind this window: the keys of the next, the words of the one after
+    int s2, m2;
+    span(k + 2, s2, m2);
+    const ulonglong2 k1 = L < m1 ? pz[(uint32_t)w1] : make_ulonglong2(0ull, 0ull);
+    const uint64_t w2 = L < m2 ? sw[s2 + L] : 0ull;
+    const bool valid = L < m0;
+    uint32_t tag;
+    if constexpr (PK) {
+      if (valid) {
+        ptw[L] = packed_test_word(k0.x, k0.y, (uint32_t)(w0 >> 32) & 63u, below);
+        paw[L] = packed_above_word(k0.x, k0.y, wa.idx);
+        pvv[L] = (uint32_t)w0;
+      }
+      tag = valid ? (uint32_t)(w0 >> 40) : 0xFFFFFFFFu;
+    } else {
+      tag = valid ? (uint32_t)b * (uint32_t)LC + (uint32_t)(w0 >> 40) : 0xFFFFFFFFu;
+      if (valid) W.st[wv][L] = make_record(w0, k0, tag);
+    }
+    lds_fence();
+    // last lane of my cell in the window (the window holds whole cells)
+    const uint32_t nxt = __shfl_down(tag, 1, 64);
+    const uint64_t bm = __ballot(L >= m0 - 1 || nxt != tag);
+    const int last = L + __builtin_ctzll(bm >> L);
+    const int rounds = valid ? last - L : 0;
+    if constexpr (PK)
+      window_tests_packed(PR, 0, rounds, (uint32_t)below, wa.nb, amask, wa.keys, wa.cap, wa.xs, ctr, W, a);
+    else
+      window_tests(W.st[wv], rounds, below, wa.nb, wa.fmask, wa.keys, wa.cap, wa.xs, ctr, W, a);
+    w0 = w1;
+    k0 = k1;
+    m0 = m1;
+    w1 = w2;
+    m1 = m2;
+  }
+}
+
+// The window pass of a bucket of n < 65536 entries whose records went through
+// memory (ents): packed windows of whole cells (the list overwrites cnt[]),
+// built by the whole workgroup from PW_MIN entries on, by wave 0 below that
+__device__ __forceinline__ void memory_windows(int64_t base, int64_t n, const CellEnt* __restrict__ ents,
+                                               const ConnectWin& wa, uint64_t below, int64_t* __restrict__ ctr,
+                                               int* cnt, const int* cur, int* nwin_s, WinLds& W, WinAcc& a) {
+  const bool par = n >= PW_MIN;
+  if (par) {
+    const int nw = build_windows_par(cnt, cur, reinterpret_cast<uint16_t*>(&W));
+    if (threadIdx.x == 0) *nwin_s = nw;
+  }
+  if (!par && tnp::wave() == 0) {
+    const int nw = build_windows(cnt, cur);
+    if (tnp::lane() == 0) *nwin_s = nw;
+  }
+  __syncthreads();
+  window_pass_packed(ents, base, reinterpret_cast<const uint32_t*>(cnt), *nwin_s, tnp::wave(), TNP_WAVES, below,
+                     wa.nb, wa.fmask, wa.keys, wa.cap, wa.xs, ctr, W, a);
+}
+
+// one workgroup per group bucket; PK: packed records (steps with packed_ok)
+template <bool PK>
+__global__ void __launch_bounds__(TNP_BLOCK, TNP_BG_MINB)
 k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __restrict__ ekv,
-               const ulonglong2* __restrict__ pz, CellEnt* __restrict__ ents, WinArgs wa, PairLists pl,
+               const ulonglong2* __restrict__ pz, CellEnt* __restrict__ ents, ConnectWin wa, PairLists pl,
                int64_t* __restrict__ ctr) {
-  constexpr int LC = 1 << (3 * SH);
   __shared__ int cnt[LC];
   __shared__ int cur[LC];
   __shared__ int64_t lds[TNP_WAVES];
   __shared__ int64_t lds3[3 * TNP_WAVES];
   __shared__ int64_t s_pk, s_sp;
   __shared__ int nwin_s;
-  constexpr bool LREC = TNP_PACKED_WIN;
-  __shared__ __attribute__((aligned(32))) unsigned char wraw[LREC ? WL_RAW : sizeof(WinLds)];
-  WinLds& W = *reinterpret_cast<WinLds*>(wraw);
-  CellEnt* const lrec = reinterpret_cast<CellEnt*>(wraw + WL_ST);
+  __shared__ WinLds W;
   const int b = blockIdx.x;
   const int64_t base = bbase[b];
   const int64_t n = bbase[b + 1] - base;
@@ -1182,269 +1240,44 @@ k_bucket_group(BGeom G, const int64_t* __restrict__ bbase, const uint64_t* __res
     pl.bcount[b] = 0;                 // passes; sub geometries: the refine pass zeroes them)
     pl.bcur[b] = 0;
   }
+  // (wa.keys == null: grouping only, no window pass.  launch_bucket_pairs
+  // never asks for it any more; the mode and the lone entry's record stay
+  // because taking them out measured 0.5 % slower at 128^3)
   if (n < 2) {
     if (threadIdx.x == 0 && wa.bstat) bucket_stats_out(wa, b, 0, 0, 0, 0, ctr);
-    if (n == 1 && threadIdx.x == 0) {  // a lone entry: a record the window pass can read
+    if (n == 1 && threadIdx.x == 0) {  // a lone entry: a record a window pass could read
       const uint64_t w = ekv[base];
-      const ulonglong2 k = pz[(uint32_t)w];
-      CellEnt r;
-      r.p = k.x;
-      r.z = k.y;
-      r.v = (int32_t)(uint32_t)w;
-      r.f = (uint32_t)(w >> 32) & 63u;
-      r.tag = (uint32_t)b * (uint32_t)LC + (uint32_t)(w >> 40);
-      r.pad = 0;
-      ents[base] = r;
+      ents[base] = make_record(w, pz[(uint32_t)w], (uint32_t)b * (uint32_t)LC + (uint32_t)(w >> 40));
     }
-  } else if (TNP_SMALL_BUCKET && wa.keys && n <= 64) {
-    if (tnp::wave() == 0) {
-      const uint64_t below = (wa.idx >= 64) ? ~0ull : ((1ull << wa.idx) - 1ull);
-      group_small<SH>(b, base, (int)n, ekv, pz, wa, below, ctr, W);
-    }
-  } else {
-    // (a bucket of one chunk gains nothing from it: bunny-scale buckets)
-    const bool in_lds = LREC && wa.keys && pl.perm && n > TNP_BG_LDS_MIN && n < 65536;
-    void* const order = !in_lds ? nullptr
-                                : SW ? static_cast<void*>(reinterpret_cast<uint64_t*>(pl.perm) + base)
-                                     : static_cast<void*>(pl.perm + base);
-    group_bucket<SH>(G, b, base, n, ekv, pz, ents, pl, ctr, cnt, cur, lds, lds3, &s_pk, &s_sp, order);
-    if (wa.keys) {
-      // the window pass over this bucket's records, right behind their
-      // stores (the workgroup's own stores: visible after the barrier)
-      __syncthreads();
-      WinAcc a;
-      const uint64_t below = (wa.idx >= 64) ? ~0ull : ((1ull << wa.idx) - 1ull);
-      const bool wave_lists = in_lds && SW && TNP_BG_WAVEWIN;
-      if (wave_lists) {
-        // each wave takes the cells whose records start in its quarter of the
-        // bucket, packs them into windows of whole cells itself (the serial
-        // walk of build_windows over a quarter of the cells) and walks its
-        // windows through a private 64-record stage in LDS: no workgroup
-        // barrier from the grouping to the statistics.  A window's records
-        // are built from the bucket's entry words in cell order and the
-        // member keys, software-pipelined (the keys of the next window and the
-        // words of the one after are in flight while a window is tested).
-        // Round 4 built one list for the bucket (the whole workgroup,
-        // pointer doubling) and tested it in shared chunks, each waiting for
-        // its slowest window.
-        const uint64_t* sw = static_cast<const uint64_t*>(order);
-        const int L = tnp::lane(), wv = tnp::wave();
-        const int nn = (int)n;
-        const int c_lo = wv == 0 ? 0 : first_cell_from<LC>(cnt, cur, (int)((int64_t)nn * wv / TNP_WAVES));
-        const int c_hi = wv == TNP_WAVES - 1 ? LC
-                                             : first_cell_from<LC>(cnt, cur, (int)((int64_t)nn * (wv + 1) / TNP_WAVES));
-        // (every wave has read the cells it bounds by before any list is written)
-        __syncthreads();
-        const int nw = uniform(build_windows_range(cnt, cur, c_lo, c_hi));
-        const uint32_t* wl = reinterpret_cast<const uint32_t*>(cnt) + c_lo;
-        auto span = [&](int k, int& s, int& m) {
-          if (k >= nw) { s = 0; m = 0; return; }
-          const uint32_t se = (uint32_t)uniform((int)wl[k]);
-          s = (int)(se & 0xFFFFu);
-          m = (int)(se >> 16) - s;
-        };
-        int s0, m0, s1, m1;
-        span(0, s0, m0);
-        span(1, s1, m1);
-        uint64_t w0 = L < m0 ? sw[s0 + L] : 0ull;
-        uint64_t w1 = L < m1 ? sw[s1 + L] : 0ull;
-        ulonglong2 k0 = L < m0 ? pz[(uint32_t)w0] : make_ulonglong2(0ull, 0ull);
-        // this wave's packed stage (64 records), laid over its W.st slots
-        uint64_t* const ptw = reinterpret_cast<uint64_t*>(&W.st[wv][0]);
-        uint64_t* const paw = ptw + 64;
-        uint32_t* const pvv = reinterpret_cast<uint32_t*>(paw + 64);
-        static_assert(64 * (8 + 8 + 4) <= sizeof(W.st[0]), "a wave's packed stage fits its record slots");
-        const PackedRecs PR{ptw, paw, pvv, nullptr};
-        uint64_t amask = 0;
-        if (PK && wa.fmask) {
-          const uint64_t lo = (uint32_t)(wa.fmask >> wa.idx);
-          amask = lo | (lo << 32);
-        }
-        for (int k = 0; k < nw; ++k) {
-          // in flight behind this window: the keys of the next, the words of the one after
-          int s2, m2;
-          span(k + 2, s2, m2);
-          const ulonglong2 k1 = L < m1 ? pz[(uint32_t)w1] : make_ulonglong2(0ull, 0ull);
-          const uint64_t w2 = L < m2 ? sw[s2 + L] : 0ull;
-          const bool valid = L < m0;
-          uint32_t tag;
-          if constexpr (PK) {
-            if (valid) {
-              ptw[L] = packed_test_word(k0.x, k0.y, (uint32_t)(w0 >> 32) & 63u, below);
-              paw[L] = packed_above_word(k0.x, k0.y, wa.idx);
-              pvv[L] = (uint32_t)w0;
-            }
-            tag = valid ? (uint32_t)(w0 >> 40) : 0xFFFFFFFFu;
-          } else {
-            CellEnt e;
-            e.p = k0.x;
-            e.z = k0.y;
-            e.v = (int32_t)(uint32_t)w0;
-            e.f = (uint32_t)(w0 >> 32) & 63u;
-            e.tag = valid ? (uint32_t)b * (uint32_t)LC + (uint32_t)(w0 >> 40) : 0xFFFFFFFFu;
-            e.pad = 0;
-            if (valid) W.st[wv][L] = e;
-            tag = e.tag;
-          }
-          lds_fence();
-          // last lane of my cell in the window (the window holds whole cells)
-          const uint32_t nxt = __shfl_down(tag, 1, 64);
-          const uint64_t bm = __ballot(L >= m0 - 1 || nxt != tag);
-          const int last = L + __builtin_ctzll(bm >> L);
-          const int rounds = valid ? last - L : 0;
-          if constexpr (PK)
-            window_tests_packed(PR, 0, rounds, (uint32_t)below, wa.nb, amask, wa.keys, wa.cap, wa.xs, ctr, W, a);
-          else
-            window_tests(W.st[wv], rounds, below, wa.nb, wa.fmask, wa.keys, wa.cap, wa.xs, ctr, W, a);
-          w0 = w1;
-          k0 = k1;
-          m0 = m1;
-          w1 = w2;
-          m1 = m2;
-        }
-      } else if (TNP_PACKED_WIN && n < 65536) {
-        // packed windows of whole cells (the list overwrites cnt[]): built by
-        // the whole workgroup for 8^3-cell buckets (their scratch fits the
-        // window pass's LDS, unused until the pass), by wave 0 for 16^3
-        bool par = false;
-        if constexpr (TNP_PAR_WIN && LC == 512) {
-          static_assert(sizeof(WinLds) >= (PW_NJ + 3) * (LC + 1) * sizeof(uint16_t) + 12 * sizeof(int),
-                        "window-builder scratch");
-          par = n >= PW_MIN;
-          if (par) {
-            const int nw = build_windows_par<LC>(cnt, cur, reinterpret_cast<uint16_t*>(&W));
-            if (threadIdx.x == 0) nwin_s = nw;
-          }
-        }
-        if (!par && tnp::wave() == 0) {
-          const int nw = build_windows<LC>(cnt, cur);
-          if (tnp::lane() == 0) nwin_s = nw;
-        }
-        __syncthreads();
-        if (in_lds) {
-          // chunks of TNP_LREC_CH record positions gathered into LDS, then the
-          // windows that start there tested.  Software-pipelined: SW (the
-          // bucket's entry words written in cell order by the grouping): the
-          // words of chunk j + 2 and the member keys of chunk j + 1 are in
-          // flight while chunk j is tested; else (cell order as entry
-          // indices) the order of j + 3, the words of j + 2, the keys of j + 1
-          const uint64_t* kv = ekv + base;
-          const int nn = (int)n;
-          constexpr int CH = TNP_LREC_CH;
-          int kw = tnp::wave();  // this wave's next window (windows kw, kw + TNP_WAVES, ...)
-          int ia[LREC_R], ib[LREC_R];
-          uint64_t wa0[LREC_R], wb[LREC_R];
-          ulonglong2 ka[LREC_R], kb[LREC_R];
-          auto in_chunk = [&](int q0, int r) {
-            const int q = q0 + r * TNP_BLOCK + threadIdx.x;
-            return q < q0 + LREC_N && q < nn;
-          };
-          auto load_i = [&](int q0, int (&ix)[LREC_R]) {
-            const int32_t* perm = static_cast<const int32_t*>(order);
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) ix[r] = in_chunk(q0, r) ? perm[q0 + r * TNP_BLOCK + threadIdx.x] : -1;
-          };
-          auto load_w = [&](const int (&ix)[LREC_R], uint64_t (&w)[LREC_R]) {
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) w[r] = ix[r] >= 0 ? kv[ix[r]] : 0ull;
-          };
-          auto load_sw = [&](int q0, uint64_t (&w)[LREC_R]) {
-            const uint64_t* sw = static_cast<const uint64_t*>(order);
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) w[r] = in_chunk(q0, r) ? sw[q0 + r * TNP_BLOCK + threadIdx.x] : 0ull;
-          };
-          auto load_k = [&](const uint64_t (&w)[LREC_R], ulonglong2 (&k)[LREC_R]) {
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) k[r] = pz[(uint32_t)w[r]];
-          };
-          if constexpr (SW) {
-            load_sw(0, wa0);
-            load_k(wa0, ka);
-            if (CH < nn) load_sw(CH, wb);
-          } else {
-            load_i(0, ia);
-            load_w(ia, wa0);
-            load_k(wa0, ka);
-            if (CH < nn) {
-              load_i(CH, ia);
-              load_w(ia, wb);
-            }
-            if (2 * CH < nn) load_i(2 * CH, ib);
-          }
-          // packed records (PK: steps with packed_ok): SoA over the same LDS
-          uint64_t* const ptw = reinterpret_cast<uint64_t*>(wraw + WL_ST);
-          uint64_t* const paw = ptw + LREC_N;
-          uint32_t* const pvv = reinterpret_cast<uint32_t*>(paw + LREC_N);
-          uint16_t* const ptg = reinterpret_cast<uint16_t*>(pvv + LREC_N);
-          static_assert(LREC_N * (8 + 8 + 4 + 2) <= WL_RAW - WL_ST, "packed records fit the record chunk");
-          const PackedRecs PR{ptw, paw, pvv, ptg};
-          uint64_t amask = 0;
-          if (PK && wa.fmask) {
-            const uint64_t lo = (uint32_t)(wa.fmask >> wa.idx);
-            amask = lo | (lo << 32);
-          }
-          for (int p0 = 0; p0 < nn; p0 += CH) {
-            const int p1 = min(nn, p0 + LREC_N);
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) {
-              const int q = p0 + r * TNP_BLOCK + threadIdx.x;
-              if (q >= p1) continue;
-              if constexpr (PK) {
-                ptw[q - p0] = packed_test_word(ka[r].x, ka[r].y, (uint32_t)(wa0[r] >> 32) & 63u, below);
-                paw[q - p0] = packed_above_word(ka[r].x, ka[r].y, wa.idx);
-                pvv[q - p0] = (uint32_t)wa0[r];
-                ptg[q - p0] = (uint16_t)(wa0[r] >> 40);
-              } else {
-                CellEnt e;
-                e.p = ka[r].x;
-                e.z = ka[r].y;
-                e.v = (int32_t)(uint32_t)wa0[r];
-                e.f = (uint32_t)(wa0[r] >> 32) & 63u;
-                e.tag = (uint32_t)b * (uint32_t)LC + (uint32_t)(wa0[r] >> 40);
-                e.pad = 0;
-                lrec[q - p0] = e;
-              }
-            }
-            __syncthreads();
-            uint64_t wc[LREC_R];
-            if (p0 + CH < nn) load_k(wb, kb);
-            if constexpr (SW) {
-              if (p0 + 2 * CH < nn) load_sw(p0 + 2 * CH, wc);
-            } else {
-              if (p0 + 2 * CH < nn) load_w(ib, wc);
-              if (p0 + 3 * CH < nn) load_i(p0 + 3 * CH, ib);
-            }
-            if constexpr (PK)
-              window_pass_packed_lds(PR, p0, p0 + CH, reinterpret_cast<const uint32_t*>(cnt), nwin_s, &kw,
-                                     TNP_WAVES, (uint32_t)below, wa.nb, amask, wa.keys, wa.cap, wa.xs, ctr, W, a);
-            else
-              window_pass_lds(lrec, p0, p0 + CH, reinterpret_cast<const uint32_t*>(cnt), nwin_s, &kw, TNP_WAVES,
-                              below, wa.nb, wa.fmask, wa.keys, wa.cap, wa.xs, ctr, W, a);
-            __syncthreads();  // (the next chunk overwrites the records)
-#pragma unroll
-            for (int r = 0; r < LREC_R; ++r) {
-              wa0[r] = wb[r];
-              ka[r] = kb[r];
-              wb[r] = wc[r];
-            }
-          }
-        } else {
-          window_pass_packed(ents, base, reinterpret_cast<const uint32_t*>(cnt), nwin_s, tnp::wave(), TNP_WAVES,
-                             below, wa.nb, wa.fmask, wa.keys, wa.cap, wa.xs, ctr, W, a);
-        }
-      } else {
-        window_pass(ents, base, base + n, tnp::wave(), TNP_WAVES, below, wa.nb, wa.fmask, wa.keys, wa.cap,
-                    wa.xs, ctr, W, a);
-      }
-      fold_wave_counts(a);
-      window_flush(wa.keys, wa.cap, wa.xs, ctr, W, a);
-      int64_t tc, tr, tx;
-      tnp::block_scan_excl(a.n_compat, lds, tc);
-      tnp::block_scan_excl(a.n_reg, lds, tr);
-      tnp::block_scan_excl(a.n_conn, lds, tx);
-      if (threadIdx.x == 0) bucket_stats_out(wa, b, tc, tr, tx, s_sp, ctr);
-    }
+    return;
   }
+  if (wa.keys && n <= 64) {
+    if (tnp::wave() == 0) group_small(b, base, (int)n, ekv, pz, wa, ctr, W);
+    return;
+  }
+  const bool in_lds = wa.keys && pl.cell_words && n > TNP_BG_LDS_MIN && n < 65536;
+  group_bucket(G, b, base, n, ekv, pz, ents, pl, ctr, cnt, cur, lds, lds3, &s_pk, &s_sp,
+               in_lds ? pl.cell_words + base : nullptr);
+  if (!wa.keys) return;
+  // the window pass over this bucket's records, right behind their stores
+  // (the workgroup's own stores: visible after the barrier)
+  __syncthreads();
+  WinAcc a;
+  const uint64_t below = (wa.idx >= 64) ? ~0ull : ((1ull << wa.idx) - 1ull);
+  if (in_lds)
+    wave_windows<PK>(b, n, pl.cell_words + base, pz, wa, below, ctr, cnt, cur, W, a);
+  else if (n < 65536)
+    memory_windows(base, n, ents, wa, below, ctr, cnt, cur, &nwin_s, W, a);
+  else  // (window offsets are 16 bits: the 32-stride pass over the records as they lie)
+    window_pass(ents, base, base + n, tnp::wave(), TNP_WAVES, below, wa.nb, wa.fmask, wa.keys, wa.cap,
+                wa.xs, ctr, W, a);
+  fold_wave_counts(a);
+  window_flush(wa.keys, wa.cap, wa.xs, ctr, W, a);
+  int64_t tc, tr, tx;
+  tnp::block_scan_excl(a.n_compat, lds, tc);
+  tnp::block_scan_excl(a.n_reg, lds, tr);
+  tnp::block_scan_excl(a.n_conn, lds, tx);
+  if (threadIdx.x == 0) bucket_stats_out(wa, b, tc, tr, tx, s_sp, ctr);
 }
 
 }  // namespace
@@ -1533,22 +1366,21 @@ int launch_bucket_refine(const BucketGeom& G, const int64_t* bbase, const uint64
 
 int launch_bucket_pairs(const BucketGeom& G, const int64_t* bbase, const uint64_t* ekv, const uint64_t* pz,
                         CellEnt* ents, int32_t* pcell, int32_t* pent, int32_t* pn, int64_t* ptoff, int32_t* bcell,
-                        int64_t bcap, int32_t* bcount, int32_t* bcur, const ConnectWin* win, int64_t* ctr,
-                        hipStream_t s, int32_t* perm) {
-  const int NB = G.NG, sh = G.sub ? 3 : G.sh;
-  const PairLists pl{pcell, pent, pn, ptoff, bcell, bcap, connect_chunk_pairs(), bcount, bcur, perm};
-  WinArgs wa{0, 0, 0ull, nullptr, 0, nullptr, nullptr, 0};
-  if (win) wa = WinArgs{win->idx, win->nb, win->fmask, win->keys, win->cap, win->xs, win->bstat, win->packed};
+                        int64_t bcap, int32_t* bcount, int32_t* bcur, const ConnectWin& win,
+                        uint64_t* cell_words, int64_t* ctr, hipStream_t s) {
+  if ((G.sub ? 3 : G.sh) != SH) {
+    tnp_set_error("bucket pairs: the group buckets are not 8^3 cells");
+    return -1;
+  }
+  const int NB = G.NG;
+  const PairLists pl{pcell, pent, pn, ptoff, bcell, bcap, connect_chunk_pairs(), bcount, bcur, cell_words};
   const ulonglong2* pz2 = reinterpret_cast<const ulonglong2*>(pz);
-  if (sh == 3 && wa.packed)
-    hipLaunchKernelGGL((k_bucket_group<3, true>), dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, wa, pl,
+  if (win.packed)
+    hipLaunchKernelGGL(k_bucket_group<true>, dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, win, pl,
                        ctr);
-  else if (sh == 3)
-    hipLaunchKernelGGL((k_bucket_group<3, false>), dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, wa,
-                       pl, ctr);
   else
-    hipLaunchKernelGGL((k_bucket_group<4, false>), dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, wa,
-                       pl, ctr);
+    hipLaunchKernelGGL(k_bucket_group<false>, dim3(NB), dim3(TNP_BLOCK), 0, s, G, bbase, ekv, pz2, ents, win, pl,
+                       ctr);
   TNP_CHECK(hipGetLastError());
   return 0;
 }

@@ -1,7 +1,6 @@
 // Connecting-edge pair test and the window pass over cell-contiguous entry
-// records (subpoly.py:484-535), shared by step.hip (k_connect, k_connect_win)
-// and bucket.hip (the grouping kernel runs the window pass over its own
-// bucket).
+// records (subpoly.py:484-535), shared by step.hip (k_connect) and
+// bucket.hip (the grouping kernel runs the window pass over its own bucket).
 #pragma once
 #include "common.h"
 #include "step.h"
@@ -109,8 +108,8 @@ __device__ __forceinline__ void lds_fence() {
 #endif
 constexpr int WOWN = TNP_WOWN;  // tests of one window resolved by table (more: binary search)
 
-// st last: the grouping kernel's LDS-record path lays its record chunk over
-// st and the space behind it (bucket.hip k_bucket_group)
+// st: a wave's 64-record stage; the grouping kernel's LDS-record path lays a
+// wave's packed stage over its slots (bucket.hip wave_windows)
 struct WinLds {
   int exc[TNP_WAVES][64];
   uint16_t own[TNP_WAVES][WOWN];  // test t -> initiator | partner << 8
@@ -228,29 +227,6 @@ __device__ __forceinline__ void window_pass_packed(const CellEnt* __restrict__ e
   }
 }
 
-// Packed windows over records already in LDS (the grouping kernel's record
-// chunk: rec[p - p0] holds the bucket's record p): the windows of wl[] from
-// this wave's cursor *k (windows k, k + dw, ...) that start before p_end
-__device__ __forceinline__ void window_pass_lds(const CellEnt* rec, int p0, int p_end, const uint32_t* wl, int nwin,
-                                                int* k, int dw, uint64_t below, int nb, uint64_t fmask,
-                                                uint64_t* __restrict__ keys, int64_t cap,
-                                                int64_t* __restrict__ xs, int64_t* __restrict__ ctr,
-                                                WinLds& W, WinAcc& a) {
-  const int L = tnp::lane();
-  for (; *k < nwin; *k += dw) {
-    const uint32_t se = (uint32_t)uniform((int)wl[*k]);
-    const int s = (int)(se & 0xFFFFu), n = (int)(se >> 16) - s;
-    if (s >= p_end) break;
-    const CellEnt* st = rec + (s - p0);
-    const bool valid = L < n;
-    const uint32_t tag = valid ? st[L].tag : 0xFFFFFFFFu;
-    const uint32_t nxt = __shfl_down(tag, 1, 64);
-    const uint64_t bm = __ballot(L >= n - 1 || nxt != tag);  // (the window holds whole cells)
-    const int last = L + __builtin_ctzll(bm >> L);
-    window_tests(st, valid ? last - L : 0, below, nb, fmask, keys, cap, xs, ctr, W, a);
-  }
-}
-
 // ---------------------------------------------------------------------------
 // Packed records (the grouping kernel's LDS-record path, steps with
 // 1 <= idx <= 29 and K - idx <= 32).  The pair test reads only the planes
@@ -267,7 +243,6 @@ struct PackedRecs {
   const uint64_t* tw;  // test words
   const uint64_t* aw;  // above words
   const uint32_t* vv;  // vertex slots
-  const uint16_t* tg;  // local cell
 };
 constexpr int PK_FLAG_SHIFT = 29;
 constexpr uint32_t PK_PLANES = (1u << PK_FLAG_SHIFT) - 1u;
@@ -365,27 +340,6 @@ __device__ __forceinline__ void window_tests_packed(const PackedRecs& R, int s, 
     append(em, key);
   }
   lds_fence();
-}
-
-// packed windows over the packed record chunk (records p0 .. of the bucket
-// at R index p - p0): as window_pass_lds
-__device__ __forceinline__ void window_pass_packed_lds(const PackedRecs& R, int p0, int p_end, const uint32_t* wl,
-                                                       int nwin, int* k, int dw, uint32_t below, int nb,
-                                                       uint64_t amask, uint64_t* __restrict__ keys, int64_t cap,
-                                                       int64_t* __restrict__ xs, int64_t* __restrict__ ctr,
-                                                       WinLds& W, WinAcc& a) {
-  const int L = tnp::lane();
-  for (; *k < nwin; *k += dw) {
-    const uint32_t se = (uint32_t)uniform((int)wl[*k]);
-    const int s = (int)(se & 0xFFFFu), n = (int)(se >> 16) - s;
-    if (s >= p_end) break;
-    const bool valid = L < n;
-    const uint32_t tag = valid ? R.tg[s - p0 + L] : 0xFFFFFFFFu;
-    const uint32_t nxt = __shfl_down(tag, 1, 64);
-    const uint64_t bm = __ballot(L >= n - 1 || nxt != tag);  // (the window holds whole cells)
-    const int last = L + __builtin_ctzll(bm >> L);
-    window_tests_packed(R, s - p0, valid ? last - L : 0, below, nb, amask, keys, cap, xs, ctr, W, a);
-  }
 }
 
 __device__ __forceinline__ void window_tests(const CellEnt* st, int rounds, uint64_t below, int nb, uint64_t fmask,

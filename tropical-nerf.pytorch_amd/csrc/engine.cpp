@@ -1765,13 +1765,13 @@ static int finish_connect(tnp_engine* e, FinishStep& f, hipStream_t s) {
                           packed_ok(idx, K) ? 1 : 0};
       // the LDS-record path's cell-order scratch (TNP_LDS_RECORDS=0: off)
       const bool lrec = e->lds_records;
-      if (lrec && buf_ensure(e->bk[4], TB * sizeof(uint64_t), s)) return -1;  // (entry words or indices)
+      if (lrec && buf_ensure(e->bk[4], TB * sizeof(uint64_t), s)) return -1;  // (entry words)
       TIMED("bucket_group", 0.0,
             launch_bucket_pairs(bg, P<int64_t>(e->bk[bg.sub ? 8 : 2]), P<uint64_t>(bg.sub ? e->sents2 : e->sents),
                                 P<uint64_t>(c.pz), P<CellEnt>(e->ents), P<int32_t>(e->pcell),
                                 P<int32_t>(e->pent), P<int32_t>(e->pcn), P<int64_t>(e->ptoff),
                                 P<int32_t>(e->bcell), bcap, P<int32_t>(e->bk[0]), P<int32_t>(e->bk[1]),
-                                &cw, ctr, s, lrec ? P<int32_t>(e->bk[4]) : nullptr));
+                                cw, lrec ? P<uint64_t>(e->bk[4]) : nullptr, ctr, s));
       e->bk_clean = true;
     } else if (!chunks_ok) {
       if (buf_ensure(e->bcell, bcap * sizeof(int32_t), s)) return -1;

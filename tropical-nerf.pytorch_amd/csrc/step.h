@@ -157,8 +157,8 @@ __device__ __forceinline__ void ent_set_keys(CellEnt2& e, const Key<2>& p, const
   e.z[1] = z.w[1];
 }
 // cells of at most WCELL members have their pairs tested by the window pass
-// (k_connect_win): a pair (j < i) of such a cell lies in the 64-entry
-// window starting at 32 * floor(j / 32)
+// (connect.h, run by the grouping kernel): a pair (j < i) of such a cell lies
+// in the 64-entry window starting at 32 * floor(j / 32)
 #ifndef TNP_WSTRIDE
 #define TNP_WSTRIDE 32
 #endif
@@ -321,8 +321,9 @@ int launch_bucket_entries(const int32_t* members, int64_t S, int64_t V, int64_t 
 // CTR_BOVF).  The pairs of the smaller cells -> ctr[CTR_SPAIRS].  Leaves
 // bcount/bcur zeroed for the next step.  launch_connect unpacks CTR_PCK;
 // the host reads R = CTR_PCK & 0xFFFFFF, pairs = CTR_PCK >> 24.
-// win != null: the grouping kernel also runs the window pass (launch_connect_win's
-// work) over each bucket's records
+// The grouping kernel also runs the window pass (win) over each bucket: the
+// pairs of the cells of <= WCELL members
+//
 // Per-XCD shards of the connect phase's appends and pair statistics.  One
 // device-scope atomic per workgroup (or per wave flush) on ONE word
 // serialises at ~11 ns (MI355X_MICROARCH.md fan-in: ~88 per microsecond);
@@ -350,27 +351,31 @@ int launch_keys_compact(const uint64_t* keys, int64_t cap, const int64_t* xs, in
 // steps whose window pass can test packed records (connect.h): the planes
 // below idx fit 29 bits beside 3 flag bits, the planes idx .. K-1 32 bits
 __host__ __device__ inline bool packed_ok(int idx, int K) { return idx >= 1 && idx <= 29 && K - idx <= 32; }
+// the window pass the grouping kernel runs over each bucket (a kernel argument)
 struct ConnectWin {
   int idx, nb;
   uint64_t fmask;
   uint64_t* keys;
   int64_t cap;
-  int64_t* xs;
-  int64_t* bstat;  // small grids (xs == null): per-bucket statistics [NB][4] that launch_connect sums
-  int packed;      // 1: the LDS-record path tests packed records (connect.h packed_ok(idx, K))
+  int64_t* xs;  // per-XCD shards of the appends and pair statistics (above); null: ctr
+  // small grids (no shards): per-bucket pair statistics [NB][4] (compatible
+  // pairs, shared regions, connecting edges, window-pass pairs), plain
+  // stores that k_connect's first workgroup sums -- instead of 4 atomics per
+  // bucket on the counter block's words (~11 ns each, serialised)
+  int64_t* bstat;
+  int packed;  // 1: the LDS-record path tests packed records (packed_ok(idx, K))
 };
+// cell_words: scratch for T entry words (8 B each), where the LDS-record path
+// keeps every bucket's entries in cell order; null: every bucket's records
+// go through memory.  A geometry whose group buckets are not 8^3 cells is an
+// error
 int launch_bucket_pairs(const BucketGeom& g, const int64_t* bbase, const uint64_t* ekv, const uint64_t* pz,
                         CellEnt* ents, int32_t* pcell, int32_t* pent, int32_t* pn, int64_t* ptoff, int32_t* bcell,
-                        int64_t bcap, int32_t* bcount, int32_t* bcur, const ConnectWin* win, int64_t* ctr,
-                        hipStream_t s, int32_t* perm = nullptr);  // perm: T int32 scratch (LDS-record path; null: off)
+                        int64_t bcap, int32_t* bcount, int32_t* bcur, const ConnectWin& win,
+                        uint64_t* cell_words, int64_t* ctr, hipStream_t s);
 constexpr int64_t PCK_CELLS = 1 << 24;  // CTR_PCK: cell count field
 // pair indices per k_connect chunk (its bcell table granularity)
 int64_t connect_chunk_pairs();
-// window pass over the cell-contiguous entries (count ctr[CTR_T]): every
-// pair of a cell of <= WCELL members, same emission rules and counters as
-// launch_connect
-int launch_connect_win(const CellEnt* ent, int idx, int nb, uint64_t fmask, uint64_t* keys, int64_t cap,
-                       int64_t* xs, int64_t* ctr, hipStream_t s);
 
 // ---- sort.hip ----
 // ascending LSD radix sort of n u64 keys on bits [0, bits); the sorted keys

@@ -622,7 +622,7 @@ constexpr int CCH = TNP_BLOCK * CIPT;   // pair indices per block
 #define TNP_CONNECT_CB 1
 #endif
 constexpr int CONNECT_CB = TNP_CONNECT_CB;  // pairs whose record loads are in flight together
-static_assert(CONNECT_CB == 0 || CIPT % CONNECT_CB == 0, "connect batches");
+static_assert(CONNECT_CB >= 1 && CIPT % CONNECT_CB == 0, "connect batches");
 
 __device__ __forceinline__ void cell_coords(int64_t cell, int NC, int cc[3]) {
   cc[2] = (int)(cell % NC) - 2;
@@ -735,34 +735,6 @@ k_connect(const int64_t* __restrict__ ptoff, const int32_t* __restrict__ pcell,
     }
     lc = lo > 0 ? lo - 1 : 0;
   }
-#if TNP_CONNECT_CB == 0
-#pragma unroll
-  for (int k = 0; k < CIPT; ++k) {
-    const int64_t p = pw + 64 * k;
-    if (p < TT) {
-      const int x = (int)(p - pb);
-      while (lc + 1 < nr && s_off[lc + 1] <= x) ++lc;
-      int i, j;
-      pair_row(x - s_off[lc], i, j);
-      const int64_t base = s_ent[lc];
-      const CellEntT<KW> eu = ent[base + i];
-      const CellEntT<KW> ev = ent[base + j];
-      const Key<KW> pu = ent_p(eu), zu = ent_z(eu), pv = ent_p(ev), zv = ent_z(ev);
-      PairTest t = pair_test(below, eu.f, pu, zu, ev.f, pv, zv);
-      if (t.compat) {
-        n_compat++;
-        n_reg += t.regions;
-        n_conn += t.emit;
-        // the step's pruning drops it anyway (keep_edge): never appended
-        if (t.emit && (!filt || tnp::key_any(((pu ^ pv) | (zu ^ zv)) & fmask))) {
-          const uint32_t vu = (uint32_t)eu.v, vv = (uint32_t)ev.v;
-          const uint32_t lo = vu < vv ? vu : vv, hi = vu < vv ? vv : vu;
-          kk[ne++] = ((uint64_t)lo << nb) | hi;
-        }
-      }
-    }
-  }
-#else
   // CB pairs at a time: locate them (LDS only), issue all 4·CB record loads
   // (unconditional: an out-of-range pair reads entry 0 of its cell), then
   // test -- CB loads in flight per lane instead of one dependent pair
@@ -832,7 +804,6 @@ k_connect(const int64_t* __restrict__ ptoff, const int32_t* __restrict__ pcell,
       }
     }
   }
-#endif
   int64_t tot;
   int64_t off = tnp::block_scan_excl((int64_t)ne, lds, tot);
   const int sh = xs ? blockIdx.x % XS_N : 0;
@@ -845,22 +816,6 @@ k_connect(const int64_t* __restrict__ ptoff, const int32_t* __restrict__ pcell,
     if (w0 + k < rc) keys[sh * rc + w0 + k] = kk[k];
   }
   add_pair_stats(n_compat, n_reg, n_conn, lds, xs, ctr);
-}
-
-// the window pass over every cell-contiguous entry (connect.h window_pass);
-// the bucket path runs it inside its grouping kernel instead
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_connect_win(const CellEnt* __restrict__ ent, int idx, int nb, uint64_t fmask,
-              uint64_t* __restrict__ keys, int64_t cap, int64_t* __restrict__ xs, int64_t* __restrict__ ctr) {
-  __shared__ WinLds W;
-  __shared__ int64_t lds[TNP_WAVES];
-  const int64_t T = ctr[CTR_T];
-  WinAcc a;
-  const uint64_t below = (idx >= 64) ? ~0ull : ((1ull << idx) - 1ull);
-  window_pass(ent, 0, T, (int64_t)blockIdx.x * TNP_WAVES + tnp::wave(), (int64_t)gridDim.x * TNP_WAVES,
-              below, nb, fmask, keys, cap, xs, ctr, W, a);
-  window_flush(keys, cap, xs, ctr, W, a);
-  add_pair_stats(a.n_compat, a.n_reg, a.n_conn, lds, xs, ctr);
 }
 
 // the shards -> ctr and the regions' output offsets; shards zeroed for the
@@ -1577,11 +1532,11 @@ int launch_entry_keys(const int32_t* ent_v, const uint32_t* ekey, int NC, int64_
 // static chunk stride never leaves a second, late wave of blocks as a tail
 // (cached per device: one process may drive several devices)
 template <typename K>
-static int resident_grid(K kernel, int slot) {
-  static int cache[2][64];
+static int resident_grid(K kernel) {
+  static int cache[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 2048;
-  int& g = cache[slot][dev];
+  int& g = cache[dev];
   if (!g) {
     int cus = 0, per_cu = 0;
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
@@ -1593,9 +1548,7 @@ static int resident_grid(K kernel, int slot) {
   }
   return g;
 }
-static int connect_grid_size() {
-  return std::max(resident_grid(k_connect<1>, 0), resident_grid(k_connect_win, 1));
-}
+static int connect_grid_size() { return resident_grid(k_connect<1>); }
 int64_t connect_chunks(int64_t TT) { return (TT + CCH - 1) / CCH; }
 int64_t connect_chunk_pairs() { return CCH; }
 int launch_chunk_cells(const int64_t* ptoff, const int32_t* pn, int64_t rcap, int32_t* bcell,
@@ -1622,13 +1575,6 @@ int launch_connect(const int64_t* ptoff, const int32_t* pcell, const int32_t* pn
                        static_cast<const CellEnt*>(ent), idx, nb,
                        filt_last >= 0 ? tnp::key_range<1>(idx, filt_last) : tnp::key_zero<1>(), keys, cap, xs, ctr,
                        bstat, nbstat);
-  TNP_CHECK(hipGetLastError());
-  return 0;
-}
-int launch_connect_win(const CellEnt* ent, int idx, int nb, uint64_t fmask, uint64_t* keys, int64_t cap,
-                       int64_t* xs, int64_t* ctr, hipStream_t s) {
-  const int grid = connect_grid_size();
-  hipLaunchKernelGGL(k_connect_win, dim3(grid), dim3(TNP_BLOCK), 0, s, ent, idx, nb, fmask, keys, cap, xs, ctr);
   TNP_CHECK(hipGetLastError());
   return 0;
 }
