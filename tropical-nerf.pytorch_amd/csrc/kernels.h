@@ -36,8 +36,7 @@ struct NetDev {
 };
 
 static inline int net_K(const NetDev& n) { return (n.num_layers - 1) * n.num_hidden + 1; }
-int net_supported(const NetDev& n);       // 1 if forward / keys / the flat steps are instantiated
-int net_supported_full(const NetDev& n);  // ... and the curve descent, training and autograd kernels
+int net_supported(const NetDev& n);  // 1 if the net's shape has kernels (every operation)
 static inline int net_kw(const NetDev& n) { return net_K(n) <= 63 ? 1 : 2; }  // sign-key words
 
 // ---- net_lv.hip: the kernels of one level count (one translation unit per
@@ -63,7 +62,7 @@ int lv_encode(const NetDev& net, const float* x01, int64_t n, float* out, hipStr
 template <int LV>
 int lv_train(const NetDev& net, const float* xyz, const float* gt, int64_t n, float T, float eik_w, int64_t eik_batch,
              double* stats, float* g_table, float* g_w, const float* gout, const float* gJ, float* g_x, hipStream_t s);
-// VJP of the forward's gathered planes / output (train_net.h k_forward_vjp)
+// VJP of the forward's gathered planes / output (train_net.h k_forward_vjp, train_wide.h)
 template <int LV>
 int lv_forward_vjp(const NetDev& net, const float* xyz, int64_t n, const float* gpl, int64_t ld, const float* gout2,
                    float* g_table, float* g_w, float* g_x, hipStream_t s);

@@ -104,14 +104,6 @@ int net_supported(const NetDev& n) {
   return 0;
 }
 
-int net_supported_full(const NetDev& n) {
-  if (n.n_levels < 2 || n.n_levels > 8) return 0;
-#define TNP_SHAPE_OK(H_, NL_) if (n.num_hidden == H_ && n.num_layers == NL_) return 1;
-  TNP_NET_SHAPES(TNP_SHAPE_OK)
-#undef TNP_SHAPE_OK
-  return 0;
-}
-
 int launch_forward(const NetDev& net, const float* xyz, int64_t n, float* pre, int64_t ld,
                    int group, hipStream_t s, float* out2, uint64_t* pos, uint64_t* zero, uint64_t* grid,
                    uint64_t* pz) {

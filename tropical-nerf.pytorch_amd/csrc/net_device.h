@@ -447,9 +447,10 @@ struct NetShape {
 #define TNP_NET_SHAPES(X) X(8, 2) X(8, 3) X(8, 4) X(16, 2) X(16, 3) X(16, 4) X(32, 2)
 // wide shapes: K = 65 or 97 planes, two-word sign keys (common.h Key<2>).
 // They run everything the K <= 63 shapes run -- the flat and curve subpoly
-// paths (the descent included), sharding, faces, Net.forward / sdf / normal
-// and the skeleton -- except the training / autograd kernels, which stay
-// with TNP_NET_SHAPES
+// paths (the descent included), sharding, faces, Net.forward / sdf / normal,
+// the skeleton, training and autograd; the last two with kernels of their
+// own (train_wide.h: a wave per 64 points on the matrix cores), the
+// TNP_NET_SHAPES with train_net.h
 #define TNP_WIDE_SHAPES(X) X(16, 5) X(32, 3) X(32, 4)
 #endif
 #define TNP_ALL_SHAPES(X) TNP_NET_SHAPES(X) TNP_WIDE_SHAPES(X)

@@ -2,8 +2,9 @@
 // -DTNP_LV=2..8, so the shape instantiations build in parallel): the fused
 // hash-grid encoding + ReLU MLP forward, the forward of a step's new
 // vertices with its epilogue, the SDF with its input gradient, the raw
-// encoding and the skeleton's tile evaluation, for every (hidden, layers)
-// shape of TNP_NET_SHAPES.
+// encoding, the skeleton's tile evaluation, the curve descent and the
+// training / autograd kernels (train_net.h; train_wide.h for the wide
+// shapes), for every (hidden, layers) shape of TNP_ALL_SHAPES.
 //
 // Reference semantics:
 //   Net.forward(x, gather=True)   tropical/stanford/model.py:52-76 (any
@@ -21,6 +22,7 @@
 #include "step.h"
 #include "descend.h"
 #include "train_net.h"
+#include "train_wide.h"
 
 #ifndef TNP_LV
 #error "net_lv.hip is compiled once per level count: -DTNP_LV=<2..8>"
@@ -402,17 +404,26 @@ k_skel_eval(NetDev net, int i0, int j0, int k0, int n0, int n1, int n2,
     TNP_SHAPE_BODY;                                          \
     break;                                                   \
   }
-#define TNP_SHAPE_SWITCH_OF(net, SHAPES)                                                            \
+#define TNP_SHAPE_SWITCH_OF(net, CASES)                                                             \
   switch ((net).num_hidden * 16 + (net).num_layers) {                                              \
-    SHAPES(TNP_SHAPE_CASE)                                                                           \
+    CASES                                                                                            \
     default:                                                                                         \
       tnp_set_error("net shape (hidden=%d, layers=%d) not instantiated for this operation",         \
                     (net).num_hidden, (net).num_layers);                                             \
       return -1;                                                                                     \
   }
-// every shape / the K <= 63 shapes (curve descent, training, autograd)
-#define TNP_SHAPE_SWITCH_ALL(net) TNP_SHAPE_SWITCH_OF(net, TNP_ALL_SHAPES)
-#define TNP_SHAPE_SWITCH(net) TNP_SHAPE_SWITCH_OF(net, TNP_NET_SHAPES)
+// every shape: one body
+#define TNP_SHAPE_SWITCH_ALL(net) TNP_SHAPE_SWITCH_OF(net, TNP_ALL_SHAPES(TNP_SHAPE_CASE))
+// every shape, the wide ones with a body of their own (TNP_SHAPE_BODY_WIDE:
+// training and autograd, train_wide.h)
+#define TNP_SHAPE_CASE_WIDE(H_, NL_)                         \
+  case H_ * 16 + NL_: {                                      \
+    constexpr int H = H_, NL = NL_;                          \
+    TNP_SHAPE_BODY_WIDE;                                     \
+    break;                                                   \
+  }
+#define TNP_SHAPE_SWITCH_SPLIT(net) \
+  TNP_SHAPE_SWITCH_OF(net, TNP_NET_SHAPES(TNP_SHAPE_CASE) TNP_WIDE_SHAPES(TNP_SHAPE_CASE_WIDE))
 
 template <>
 int lv_forward<LVC>(const NetDev& net, const float* xyz, int64_t n, float* pre, int64_t ld, int group,
@@ -478,8 +489,15 @@ int lv_train<LVC>(const NetDev& net, const float* xyz, const float* gt, int64_t 
                        stats);                                                                                    \
   hipLaunchKernelGGL((k_train_grads<LVC, H, NL>), dim3(tnp_grid(n)), dim3(TNP_BLOCK), 0, s, net, xyz, gt, n, T,    \
                      eik_w, eik_batch, stats, g_table, g_w, gout, gJ, g_x);
-  TNP_SHAPE_SWITCH(net)
+#define TNP_SHAPE_BODY_WIDE                                                                                       \
+  if (train)                                                                                                      \
+    hipLaunchKernelGGL((k_train_norms_wide<LVC, H, NL>), dim3(tnp_grid(n, TW_BLOCK)), dim3(TW_BLOCK), 0, s, net,  \
+                       xyz, gt, n, T, stats);                                                                     \
+  hipLaunchKernelGGL((k_train_grads_wide<LVC, H, NL>), dim3(tnp_grid(n, TW_BLOCK)), dim3(TW_BLOCK), 0, s, net,    \
+                     xyz, gt, n, T, eik_w, eik_batch, stats, g_table, g_w, gout, gJ, g_x);
+  TNP_SHAPE_SWITCH_SPLIT(net)
 #undef TNP_SHAPE_BODY
+#undef TNP_SHAPE_BODY_WIDE
   TNP_CHECK(hipGetLastError());
   return 0;
 }
@@ -490,8 +508,12 @@ int lv_forward_vjp<LVC>(const NetDev& net, const float* xyz, int64_t n, const fl
 #define TNP_SHAPE_BODY                                                                                           \
   hipLaunchKernelGGL((k_forward_vjp<LVC, H, NL>), dim3(tnp_grid(n)), dim3(TNP_BLOCK), 0, s, net, xyz, n, gpl, ld, \
                      gout2, g_table, g_w, g_x);
-  TNP_SHAPE_SWITCH(net)
+#define TNP_SHAPE_BODY_WIDE                                                                                      \
+  hipLaunchKernelGGL((k_forward_vjp_wide<LVC, H, NL>), dim3(tnp_grid(n, TW_BLOCK)), dim3(TW_BLOCK), 0, s, net,   \
+                     xyz, n, gpl, ld, gout2, g_table, g_w, g_x);
+  TNP_SHAPE_SWITCH_SPLIT(net)
 #undef TNP_SHAPE_BODY
+#undef TNP_SHAPE_BODY_WIDE
   TNP_CHECK(hipGetLastError());
   return 0;
 }

@@ -1,7 +1,7 @@
 // SDF training on the device (reference train.py:169-224,
 // dataset.py:80-96): the launchers of the closed-form batch gradient and the
-// autograd VJPs (kernels in train_net.h, one translation unit per level count
-// through net_lv.hip), and the mesh signed distances the dataset samples.
+// autograd VJPs (kernels in train_net.h and, for the wide shapes,
+// train_wide.h; one translation unit per level count through net_lv.hip), and the mesh signed distances the dataset samples.
 #include <algorithm>
 
 #include "common.h"
@@ -155,7 +155,7 @@ __global__ void k_fill_u32(uint32_t* __restrict__ p, int64_t n, uint32_t v) {
 }  // namespace
 
 static int train_net_ok(const NetDev& net, const char* what) {
-  if (!net_supported_full(net) || net.tied) {
+  if (!net_supported(net) || net.tied) {
     tnp_set_error("%s: net shape (levels=%d, layers=%d, hidden=%d) not instantiated", what, net.n_levels,
                   net.num_layers, net.num_hidden);
     return -1;

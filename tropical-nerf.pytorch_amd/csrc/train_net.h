@@ -1,6 +1,7 @@
-// Parameter gradients of the net for training and autograd, every
-// instantiated shape (TNP_NET_SHAPES x levels 2..8): included by net_lv.hip
-// (one translation unit per level count: lv_train, lv_forward_vjp).
+// Parameter gradients of the net for training and autograd, the shapes of
+// K <= 63 planes (TNP_NET_SHAPES x levels 2..8; the wide shapes: train_wide.h,
+// the same mathematics and arguments): included by net_lv.hip (one
+// translation unit per level count: lv_train, lv_forward_vjp).
 //
 // Loss of one training batch of n points x (train.py:181-201, Net.sdf =
 // tanh(o1 - o0), model.py:84-87):

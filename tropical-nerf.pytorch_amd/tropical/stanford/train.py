@@ -23,13 +23,16 @@ of them, the state_dict saved to the cache path.  The Stanford scans are not
 part of this repository: pass --mesh PATH (any closed PLY mesh) when the
 dataset's own file is absent.  Extra flags: --weights PATH loads a
 state_dict from PATH instead of the cache location; --epochs overrides
-EPOCH (train.py:67).
+EPOCH (train.py:67); --layers / --hidden pick another net shape than the
+reference's 3 x 16 (any shape the library has kernels for, `supported_shapes`;
+model and mesh file names then carry a `_l{layers}h{hidden}` suffix).
 """
 from __future__ import annotations
 
 import argparse
 import os
 import random
+import re
 import sys
 import time
 
@@ -37,6 +40,7 @@ import numpy as np
 import torch
 
 import tropical.subpoly as sp
+from tropical._buildid import CSRC
 from tropical.stanford.model import Net
 from tropical.utils.chamfer_distance import chamfer_distance, sample_surface_from_rays
 from tropical.utils.marching_cubes import marching_cubes_torch
@@ -46,6 +50,41 @@ DIM = 3
 CANVAS_SIZE = 1.2
 R = 0.8  # StanfordDataset.R (dataset.py:27): the scans are scaled into [-R, R]
 MC_SIZES = [512, 16, 24, 32, 40, 48, 56, 64, 128, 192, 224, 256]
+
+
+def supported_shapes():
+    """The (layers, hidden) shapes the library has kernels for, read from the
+    one list it is compiled from (csrc/net_device.h TNP_NET_SHAPES and
+    TNP_WIDE_SHAPES, the full build's definitions); None when the sources are
+    not next to the package -- the library itself then refuses an
+    uninstantiated shape at its first call."""
+    try:
+        with open(os.path.join(CSRC, "net_device.h")) as fh:
+            src = fh.read()
+    except OSError:
+        return None
+    shapes = []
+    for macro in ("TNP_NET_SHAPES", "TNP_WIDE_SHAPES"):
+        bodies = re.findall(rf"^#define {macro}\(X\)(.*)$", src, flags=re.M)
+        if not bodies:
+            return None
+        body = max(bodies, key=len)  # (the experiment build's list is a subset)
+        shapes += [(int(nl), int(h)) for h, nl in re.findall(r"X\((\d+),\s*(\d+)\)", body)]
+    return sorted(shapes)
+
+
+def check_shape(num_layers: int, num_hidden: int):
+    """ValueError for a net shape without kernels, naming the supported ones."""
+    shapes = supported_shapes()
+    if shapes is not None and (num_layers, num_hidden) not in shapes:
+        names = ", ".join(f"{nl} x {h}" for nl, h in shapes)
+        raise ValueError(f"no kernels for a net of {num_layers} layers x {num_hidden} hidden units; "
+                         f"supported (layers x hidden): {names}")
+
+
+def shape_suffix(num_layers: int = 3, num_hidden: int = 16) -> str:
+    """File-name suffix of a net shape: empty for the reference's 3 x 16."""
+    return "" if (num_layers, num_hidden) == (3, 16) else f"_l{num_layers}h{num_hidden}"
 
 
 def parse_args(argv=None):
@@ -65,19 +104,30 @@ def parse_args(argv=None):
     p.add_argument("--mesh", default=None, help="training mesh (PLY) instead of the dataset's scan file")
     p.add_argument("--epochs", default=None, type=int, help="training epochs (default: the reference's EPOCH)")
     p.add_argument("--out", default="meshes", help="mesh output directory")
-    return p.parse_args(argv)
+    p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
+    p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
+    args = p.parse_args(argv)
+    try:
+        check_shape(args.layers, args.hidden)
+    except ValueError as e:
+        p.error(str(e))
+    return args
 
 
-def net_config(model_size: str, dataset: str) -> dict:
-    """train.py:70-82 (T defaults to 19 where the reference leaves it unset)."""
+def net_config(model_size: str, dataset: str, num_layers: int = 3, num_hidden: int = 16) -> dict:
+    """train.py:70-82 (T defaults to 19 where the reference leaves it unset);
+    the reference's nets are 3 x 16."""
+    check_shape(num_layers, num_hidden)
     r_min, r_max = {"small": (2, 32), "medium": (4, 64), "large": (8, 128)}[model_size]
     T = 21 if (model_size == "large" and "bunny" in dataset.lower()) else 19
-    return dict(num_layers=3, num_hidden=16, levels=4, r_min=r_min, r_max=r_max, T=T)
+    return dict(num_layers=num_layers, num_hidden=num_hidden, levels=4, r_min=r_min, r_max=r_max, T=T)
 
 
-def model_path(dataset: str, model_size: str, seed: int) -> str:
-    return os.path.join(os.path.dirname(__file__),
-                        f"models/{dataset}/{dataset}_sdf_{model_size}_{seed}.pth")
+def model_path(dataset: str, model_size: str, seed: int, num_layers: int = 3, num_hidden: int = 16) -> str:
+    """The cache path: the reference's name for its 3 x 16 nets, a shape
+    suffix for any other (a cached 3 x 16 state_dict never meets a wider net)."""
+    return os.path.join(os.path.dirname(__file__), f"models/{dataset}/{dataset}_sdf_{model_size}_{seed}"
+                                                   f"{shape_suffix(num_layers, num_hidden)}.pth")
 
 
 @torch.no_grad()
@@ -200,8 +250,8 @@ def main(argv=None):
     np.random.seed(seed)
     if not torch.cuda.is_available():
         raise SystemExit("tropical.stanford.train needs a ROCm GPU (no CPU fallback)")
-    net = Net(**net_config(args.model_size, args.dataset)).cuda()
-    path = args.weights or model_path(args.dataset, args.model_size, seed)
+    net = Net(**net_config(args.model_size, args.dataset, args.layers, args.hidden)).cuda()
+    path = args.weights or model_path(args.dataset, args.model_size, seed, args.layers, args.hidden)
     if (args.cache or args.weights) and os.path.isfile(path):
         sd = torch.load(path, map_location=net.device(), weights_only=True)
         net.load_state_dict(sd)
@@ -219,7 +269,7 @@ def main(argv=None):
     our_mesh = Mesh(verts, np.asarray(faces_with_indices, dtype=np.int64))
     print(f"Ours: {our_mesh.vertices.shape}/{our_mesh.faces.shape}")
     out_dir = os.path.join(args.out, args.dataset)
-    tag = f"{args.model_size}_{seed}"
+    tag = f"{args.model_size}_{seed}{shape_suffix(args.layers, args.hidden)}"
     our_mesh.export(os.path.join(out_dir, f"our_mesh_{tag}.ply"))
     if not args.eval:
         return 0
