@@ -421,6 +421,35 @@ int tnp_raycaster_cast(tnp_raycaster* rc, const float* d_o, const float* d_d, in
 int tnp_nn_min_dist(const float* d_a, int64_t na, const float* d_b, int64_t nb, float* d_out,
                     void* stream);
 
+/* ---- marching tetrahedra (tropical/utils/mtet.py; csrc/mtet.hip) -------- */
+
+/* marching_tetrahedras(vertices fp32 [n_points][3], tets int64 [n_tets][4]
+ * (16-byte aligned), sdf fp32 [n_points]) in three calls; the caller
+ * allocates the outputs from the counts in between.  n_points < 2^31.
+ * Inside is sdf > 0; a tet whose det[(b-a), (c-a), (d-a)] (double) is
+ * negative has its first two ids swapped IN d_tets.
+ *   classify: d_case uint8 [n_tets], d_tile int64 [3 * (tiles + 1) + 2] with
+ *     tiles = ceil(n_tets / 256) (scanned per-tile counts, kept for the next
+ *     two calls); returns the number of crossed-edge keys and of 1- and
+ *     2-triangle tets.  Returns 1 when an id lies outside [0, n_points): such
+ *     a tet is never gathered from.
+ *   edges: d_keys uint64 [2 * n_keys]; leaves the unique crossed edges
+ *     lo << nb | hi (nb = bits of n_points) sorted in d_keys[0, n_verts).
+ *   emit: verts fp32 [n_verts][3], interp int64 [n_verts][2] (the edge ends,
+ *     lo < hi, 16-byte aligned), faces int64 [n_one + 2 n_two][3] and tet_idx
+ *     int64 [n_one + 2 n_two]: the 1-triangle tets in tet order, then the
+ *     2-triangle tets in tet order.  Vertex i is the i-th edge in the
+ *     lexicographic order of (lo, hi). */
+int tnp_mt_classify(const float* d_vertices, const float* d_sdf, int64_t n_points, int64_t* d_tets,
+                    int64_t n_tets, uint8_t* d_case, int64_t* d_tile, int64_t* n_keys,
+                    int64_t* n_one, int64_t* n_two, void* stream);
+int tnp_mt_edges(const int64_t* d_tets, int64_t n_tets, int64_t n_points, const uint8_t* d_case,
+                 int64_t* d_tile, int64_t n_keys, uint64_t* d_keys, int64_t* n_verts, void* stream);
+int tnp_mt_emit(const float* d_vertices, const float* d_sdf, int64_t n_points, const int64_t* d_tets,
+                int64_t n_tets, const uint8_t* d_case, const int64_t* d_tile, const uint64_t* d_keys,
+                int64_t n_verts, int64_t n_one, float* d_verts, int64_t* d_interp, int64_t* d_faces,
+                int64_t* d_tet_idx, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

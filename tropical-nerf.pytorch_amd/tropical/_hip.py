@@ -117,6 +117,9 @@ SIGNATURES = {
                                       C.POINTER(C.c_float), _VP]),
     "tnp_raycaster_cast": (C.c_int, [_VP, _VP, _VP, _I64, _VP, _VP, _VP]),
     "tnp_nn_min_dist": (C.c_int, [_VP, _I64, _VP, _I64, _VP, _VP]),
+    "tnp_mt_classify": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _P64, _P64, _P64, _VP]),
+    "tnp_mt_edges": (C.c_int, [_VP, _I64, _I64, _VP, _VP, _I64, _VP, _P64, _VP]),
+    "tnp_mt_emit": (C.c_int, [_VP, _VP, _I64, _VP, _I64, _VP, _VP, _VP, _I64, _I64, _VP, _VP, _VP, _VP, _VP]),
     "tnp_engine_kernel_stat": (C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_double),
                                          _P64, C.POINTER(C.c_double)]),
 }
