@@ -231,6 +231,45 @@ int tnp_engine_faces(tnp_engine* eng, void* stream, int64_t* n_tri, int64_t* n_f
 int tnp_engine_faces_export(tnp_engine* eng, int64_t* d_tri, float* d_faces,
                             void* stream);
 
+/* The surface as convex polygons: final row f of extract_faces (subpoly.py:620 order), its members in
+ * the angular order of sort_polygon_vertices_batch, -1 pads dropped, ids de-duplicated keeping the first
+ * (tensor_to_triangle_faces, subpoly.py:702-704), rows left with < 3 ids omitted. Fan-triangulating
+ * polygon f as (p0, p[t+1], p[t+2]) and listing the triangles t-major is exactly tnp_engine_faces' tri.
+ * The rows of a tnp_engine_faces call on the same complex, net and eps are reused (either order of
+ * the two calls); a later tnp_engine_faces or another complex replaces the polygons held for export. */
+int tnp_engine_polygons(tnp_engine* eng, void* stream, int64_t* n_poly, int64_t* n_idx);
+/* offsets int64[n_poly+1], indices int64[n_idx] (surface vertex ids, as faces_with_indices),
+ * normals float[n_poly*3] (the row's SDF gradient at its mean point, subpoly.py:635, not normalised);
+ * any may be NULL; destinations on the device or in pinned host memory, as tnp_engine_faces_export. */
+int tnp_engine_polygons_export(tnp_engine* eng, int64_t* d_offsets, int64_t* d_indices,
+                               float* d_normals, void* stream);
+
+/* Closedness, orientation and planarity of any polygon soup: polygon p is
+ * d_indices[d_offsets[p] .. d_offsets[p+1]) over d_xyz (V x 3 fp32), all on the device.
+ *  - The edges of a polygon are its consecutive pairs, cyclic (last, first included); the
+ *    undirected key of an edge (a, b) is (min, max).  n_edges counts distinct undirected edges.
+ *  - An edge used u times (over all polygons) is boundary (u = 1), manifold (u = 2) or
+ *    non-manifold (u > 2).  e_misoriented counts the edges with u = 2 that both polygons
+ *    traverse in the same direction (a consistently oriented surface has none).
+ *  - n_vertices_used: distinct ids that occur; euler = n_vertices_used - n_edges + n_polygons.
+ *  - Geometry in fp32, Newell about the mean c of the members: N = 1/2 sum_i (p_i - c) x (p_i+1 - c);
+ *    a polygon's area is |N|, its planarity deviation dev = max_i |(p_i - c) . N| / |N| (0 when |N| = 0).
+ *    area: the sum of the per-polygon areas in double, reduced in a fixed order (the same bits on
+ *    every call with the same input); max_dev: the largest dev.
+ * d_area / d_dev (P floats each, may be NULL) receive the per-polygon values.
+ * Checked on the device before anything is read through an id, -1 with the first offender in
+ * tnp_last_error(): offsets not starting at 0 or decreasing, a polygon with fewer than 3 ids
+ * (the first such polygon); then an id outside [0, V), two equal consecutive ids, cyclic (the
+ * first such index position).  V >= 2^31 is refused.  P = 0: all zero.  Synchronises `stream`. */
+typedef struct tnp_polygon_stats {
+  int64_t n_polygons, n_indices, max_degree, n_vertices_used;
+  int64_t n_edges, e_boundary, e_manifold, e_nonmanifold, e_misoriented;
+  int64_t euler;            /* n_vertices_used - n_edges + n_polygons */
+  double area; float max_dev;
+} tnp_polygon_stats;
+int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
+                       int64_t P, tnp_polygon_stats* h_out, float* d_area, float* d_dev, void* stream);
+
 /* 1: subpoly_(..., force=False) -- the curve-approximation branch
  * (subpoly.py:120-177, 201-207; geometry.py:24-138, 259-299;
  * subpoly_debug.py:121-165, 234-271): new vertices of non-axis-aligned split

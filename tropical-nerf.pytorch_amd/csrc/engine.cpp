@@ -256,6 +256,14 @@ struct tnp_engine {
   Buf tri, faces;
   Buf tied_table;  // level-interleaved copy of the caller's table (NetDev::tied)
   int64_t n_tri = 0, n_faces = 0, dbg_F = 0, dbg_W = 0;
+  // the final rows of extract_faces (faces_rows: F1-F4) are in the face
+  // scratch for the loaded complex, net and eps; cleared by whatever changes
+  // one of the three.  rows_F rows, the largest member count (all members /
+  // those off the origin)
+  bool rows_valid = false;
+  int64_t rows_F = 0, rows_maxc = 0, rows_maxnz = 0;
+  int64_t n_poly = 0, n_pidx = 0;  // the last tnp_engine_polygons (poly_valid: still in the scratch)
+  bool poly_valid = false;
   // look-back states (a kernel may run two chains): [0] ticket counter,
   // [1..] tile status words; tickets issued so far; launch epoch
   Buf lb[2];
@@ -474,6 +482,7 @@ static int set_alive(tnp_engine* e, int64_t from, int64_t n, hipStream_t s) {
 // a freshly loaded complex: every slot live, ids dense, edge masks to compute
 static int reset_live(tnp_engine* e, hipStream_t s, bool edges_changed = true) {
   if (edges_changed) e->masks_valid = false;
+  e->rows_valid = false;  // (load, lattice, skeleton, surface, a compaction: other vertex ids)
   e->valid = true;
   e->dirty = false;
   e->V_live = e->V;
@@ -768,6 +777,7 @@ static bool levels_tied(const tnp_net* n) {
 extern "C" int tnp_engine_set_net(tnp_engine* e, const tnp_net* n) {
   if (check_net(n)) return -1;
   TNP_CHECK(hipSetDevice(e->device));
+  e->rows_valid = false;
   e->net = to_dev(n);
   if (levels_tied(n)) {
     const int L = n->n_levels;
@@ -874,6 +884,7 @@ static int set_edges_i64(tnp_engine* e, const int64_t* d_edges, int64_t E, hipSt
 extern "C" int tnp_engine_load(tnp_engine* e, const float* d_xyz, int64_t V, const int64_t* d_edges,
                                int64_t E, const float* d_pre, int keep_all, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  e->rows_valid = false;
   if (!e->has_net) { tnp_set_error("engine has no net"); return -1; }
   TNP_CHECK(hipSetDevice(e->device));
   span_all(e);  // anywhere (tnp_engine_set_span narrows it)
@@ -1256,6 +1267,7 @@ static int flat_forward_new(tnp_engine* e, int idx, int64_t n, hipStream_t s) {
 extern "C" int tnp_engine_split(tnp_engine* e, int idx, void* stream, int64_t* S_out, int32_t* fail) {
   hipStream_t s = (hipStream_t)stream;
   TNP_CHECK(hipSetDevice(e->device));
+  e->rows_valid = false;
   if (idx < e->valid_from || idx >= e->K) {
     tnp_set_error("plane %d not cached (valid from %d)", idx, e->valid_from);
     return -1;
@@ -1971,6 +1983,7 @@ static int finish_prune(tnp_engine* e, FinishStep& f, hipStream_t s) {
 extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override_, void* stream,
                                  tnp_step_stats* st) {
   hipStream_t s = (hipStream_t)stream;
+  e->rows_valid = false;
   TNP_CHECK(hipSetDevice(e->device));
   if (e->pend_idx != idx) { tnp_set_error("finish(%d) without split(%d)", idx, idx); return -1; }
   if (require_valid(e, "finish")) return -1;
@@ -2048,6 +2061,7 @@ extern "C" int tnp_engine_finish(tnp_engine* e, int idx, int prune, int override
 extern "C" int tnp_engine_run_steps(tnp_engine* e, void* stream, tnp_step_stats* stats, int max_stats,
                                     int* n_steps) {
   *n_steps = 0;
+  e->rows_valid = false;
   if (e->shards > 1) {
     tnp_set_error("run_steps: a sharded engine takes its global decisions between split and finish");
     return -1;
@@ -2114,6 +2128,7 @@ extern "C" int tnp_engine_export(tnp_engine* e, float* d_xyz, int64_t* d_edges, 
 extern "C" int tnp_engine_surface(tnp_engine* e, void* stream, int64_t* V_out, int64_t* E_out) {
   hipStream_t s = (hipStream_t)stream;
   TNP_CHECK(hipSetDevice(e->device));
+  e->rows_valid = false;
   if (require_valid(e, "surface")) return -1;
   if (compact_now(e, s)) return -1;
   const int64_t V = e->V, E = e->E;
@@ -2220,6 +2235,7 @@ __global__ void k_lattice_edges(int nx, int ny, int nz, int32_t* __restrict__ ed
 extern "C" int tnp_engine_lattice_box(tnp_engine* e, const int32_t* lo3, const int32_t* hi3, int keep_all,
                                       void* stream, int64_t* V_out, int64_t* E_out) {
   hipStream_t s = (hipStream_t)stream;
+  e->rows_valid = false;
   if (!e->has_net) { tnp_set_error("engine has no net"); return -1; }
   TNP_CHECK(hipSetDevice(e->device));
   const int N = e->net.n_marks;
@@ -2349,6 +2365,7 @@ static std::vector<SkelTile> skeleton_tiles(int L, int unit) {
 static int skeleton_build(tnp_engine* e, int unit, float size, int mode, const int32_t* box_lo,
                           const int32_t* box_hi, const unsigned int* tile_gmax, hipStream_t s, int64_t* V_out,
                           int64_t* E_out) {
+  e->rows_valid = false;
   if (!e->has_net) { tnp_set_error("engine has no net"); return -1; }
   if (unit < 2) { tnp_set_error("unit must be >= 2"); return -1; }
   TNP_CHECK(hipSetDevice(e->device));
@@ -2478,6 +2495,7 @@ extern "C" int tnp_engine_skeleton_mode(tnp_engine* e, int unit, float size, int
 extern "C" int tnp_engine_skeleton_gmax(tnp_engine* e, int unit, int rank, int world, uint32_t* h_gmax,
                                         int64_t* h_load, int cap, int* n_tiles, void* stream) {
   hipStream_t s = (hipStream_t)stream;
+  e->rows_valid = false;
   if (!e->has_net) { tnp_set_error("engine has no net"); return -1; }
   if (unit < 2 || world < 1 || rank < 0 || rank >= world) {
     tnp_set_error("skeleton_gmax: unit %d, rank %d of %d", unit, rank, world);
@@ -2544,20 +2562,23 @@ extern "C" int tnp_engine_skeleton_box(tnp_engine* e, int unit, const int32_t* l
 
 enum { FS_TABLE, FS_CNT, FS_KC, FS_KF, FS_MEMOFF, FS_RID, FS_MEM, FS_CUR, FS_ROFF, FS_RCNT,
        FS_BCNT, FS_BOFF, FS_BCUR, FS_ROWS, FS_KEEP, FS_KOFF, FS_FROW, FS_MEAN, FS_NRM, FS_SDF,
-       FS_KEY, FS_ORDV, FS_CALL, FS_CNZ, FS_HIST, FS_BASE, FS_N };
+       FS_KEY, FS_ORDV, FS_CALL, FS_CNZ, FS_HIST, FS_BASE, FS_POFF, FS_PIDX, FS_N };
 
-extern "C" int tnp_engine_faces(tnp_engine* e, void* stream, int64_t* n_tri, int64_t* n_faces) {
-  hipStream_t s = (hipStream_t)stream;
-  TNP_CHECK(hipSetDevice(e->device));
-  if (require_valid(e, "faces")) return -1;
+// F1-F4: the final rows of extract_faces on the current complex.  Leaves, for
+// rows_F rows, the row list (FS_FROW), every row's members in angular order
+// (FS_ORDV at FS_ROFF of its row), their count (FS_CALL; FS_CNZ: those off
+// the origin) and the normal that ordered them (FS_NRM) in the face scratch,
+// and sets rows_valid: tnp_engine_faces (F5) and tnp_engine_polygons (F6)
+// both emit from them.
+static int faces_rows(tnp_engine* e, hipStream_t s) {
+  e->rows_valid = e->poly_valid = false;
+  e->rows_F = e->rows_maxc = e->rows_maxnz = 0;
   if (compact_now(e, s)) return -1;
   static_assert(FS_N <= 32, "face scratch slots");
   Buf* fs = e->fscr2;
   const int64_t V = e->V;
   const int K = e->K;
-  e->n_tri = e->n_faces = 0;
-  *n_tri = *n_faces = 0;
-  if (V == 0) return 0;
+  if (V == 0) { e->rows_valid = true; return 0; }
   if (e->net.n_marks + 2 >= 1024) {
     tnp_set_error("faces: region keys hold n_marks + 2 < 1024 cells per axis");
     return -1;
@@ -2633,7 +2654,7 @@ extern "C" int tnp_engine_faces(tnp_engine* e, void* stream, int64_t* n_tri, int
     tnp_set_error("faces: a region with %d vertices (degenerate complex)", width);
     return -1;
   }
-  if (R == 0) return 0;
+  if (R == 0) { e->rows_valid = true; return 0; }
   // F2: member lists (k, v)-sorted
   if (buf_ensure(fs[FS_MEM], Mtot * 8, s) || buf_ensure(fs[FS_ROFF], R * 8, s) ||
       buf_ensure(fs[FS_RCNT], R * 4, s))
@@ -2697,11 +2718,32 @@ extern "C" int tnp_engine_faces(tnp_engine* e, void* stream, int64_t* n_tri, int
   TIMED("faces_fan_width", 8.0 * F,
         launch_max_i32(P<int32_t>(fs[FS_CALL]), F, ctr + CTR_TRI, s, P<int32_t>(fs[FS_CNZ]), ctr + CTR_FACES));
   if (read_ctr(e, s)) return -1;
+  e->rows_F = F;
+  e->rows_maxc = e->h_ctr[CTR_TRI];
+  e->rows_maxnz = e->h_ctr[CTR_FACES];
+  e->rows_valid = true;
+  return 0;
+}
+
+extern "C" int tnp_engine_faces(tnp_engine* e, void* stream, int64_t* n_tri, int64_t* n_faces) {
+  hipStream_t s = (hipStream_t)stream;
+  TNP_CHECK(hipSetDevice(e->device));
+  e->n_tri = e->n_faces = 0;
+  *n_tri = *n_faces = 0;
+  if (require_valid(e, "faces")) return -1;
+  if (faces_rows(e, s)) return -1;
+  Buf* fs = e->fscr2;
+  const int64_t F = e->rows_F;
+  if (F == 0) return 0;
+  const int32_t* frow = P<int32_t>(fs[FS_FROW]);
+  const int64_t* roff = P<int64_t>(fs[FS_ROFF]);
+  const int32_t* rcnt = P<int32_t>(fs[FS_RCNT]);
+  const float* xyz = P<float>(e->cur.xyz);
   // F5: fan triangles, fan-position-major
   const int64_t nb = fan_blocks(F);
   for (int floats = 0; floats < 2; ++floats) {
     const int32_t* cnt = P<int32_t>(fs[floats ? FS_CNZ : FS_CALL]);
-    int T = (int)e->h_ctr[floats ? CTR_FACES : CTR_TRI] - 2;
+    int T = (int)(floats ? e->rows_maxnz : e->rows_maxc) - 2;
     if (T <= 0) continue;
     if (buf_ensure(fs[FS_HIST], (int64_t)T * nb * 4, s) || buf_ensure(fs[FS_BASE], (int64_t)T * nb * 8, s))
       return -1;
@@ -2737,6 +2779,63 @@ extern "C" int tnp_engine_faces_export(tnp_engine* e, int64_t* d_tri, float* d_f
   return 0;
 }
 
+// The final rows as polygons (F6).  Every final row is a polygon: a row has
+// >= 3 members (k_keep_counts drops smaller regions before any row exists)
+// and a region's members are distinct vertices, so the de-duplication and the
+// < 3 filter of tensor_to_triangle_faces never remove anything -- polygon f is
+// row f, and FS_NRM (one normal per row) is already the [P, 3] normal array.
+extern "C" int tnp_engine_polygons(tnp_engine* e, void* stream, int64_t* n_poly, int64_t* n_idx) {
+  hipStream_t s = (hipStream_t)stream;
+  TNP_CHECK(hipSetDevice(e->device));
+  e->n_poly = e->n_pidx = 0;
+  e->poly_valid = false;
+  *n_poly = *n_idx = 0;
+  if (require_valid(e, "polygons")) return -1;
+  if (!e->rows_valid && faces_rows(e, s)) return -1;
+  Buf* fs = e->fscr2;
+  const int64_t F = e->rows_F;
+  if (buf_ensure(fs[FS_POFF], (F + 1) * sizeof(int64_t), s)) return -1;
+  if (F == 0) {  // offsets [0]
+    TNP_CHECK(hipMemsetAsync(fs[FS_POFF].p, 0, sizeof(int64_t), s));
+    TNP_CHECK(hipStreamSynchronize(s));
+    e->poly_valid = true;
+    return 0;
+  }
+  if (scan_counts(e, P<int32_t>(fs[FS_CALL]), P<int64_t>(fs[FS_POFF]), F, CTR_AUX, s)) return -1;
+  if (read_ctr(e, s)) return -1;
+  const int64_t n = e->h_ctr[CTR_AUX];
+  if (buf_ensure(fs[FS_PIDX], std::max<int64_t>(n, 1) * sizeof(int64_t), s)) return -1;
+  // 4 n member ids in, 8 n indices + 8 F offsets out; the search's offset and
+  // row-start reads hit the cache (8 F + 12 F bytes from memory once)
+  TIMED("faces_poly_emit", 12.0 * n + 28.0 * F,
+        launch_poly_emit(n, F, P<int64_t>(fs[FS_POFF]), P<int32_t>(fs[FS_FROW]), P<int64_t>(fs[FS_ROFF]),
+                         P<int32_t>(fs[FS_ORDV]), P<int64_t>(fs[FS_PIDX]), s));
+  TNP_CHECK(hipStreamSynchronize(s));
+  e->n_poly = *n_poly = F;
+  e->n_pidx = *n_idx = n;
+  e->poly_valid = true;
+  return 0;
+}
+
+extern "C" int tnp_engine_polygons_export(tnp_engine* e, int64_t* d_offsets, int64_t* d_indices, float* d_normals,
+                                          void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  TNP_CHECK(hipSetDevice(e->device));
+  Buf* fs = e->fscr2;
+  if (!e->poly_valid) {
+    tnp_set_error("polygons_export: no polygons in the engine (call tnp_engine_polygons; a later "
+                  "tnp_engine_faces or another complex replaces them)");
+    return -1;
+  }
+  if (d_offsets)
+    TNP_CHECK(hipMemcpyAsync(d_offsets, fs[FS_POFF].p, (e->n_poly + 1) * sizeof(int64_t), hipMemcpyDefault, s));
+  if (d_indices && e->n_pidx > 0)
+    TNP_CHECK(hipMemcpyAsync(d_indices, fs[FS_PIDX].p, e->n_pidx * sizeof(int64_t), hipMemcpyDefault, s));
+  if (d_normals && e->n_poly > 0)
+    TNP_CHECK(hipMemcpyAsync(d_normals, fs[FS_NRM].p, e->n_poly * 3 * sizeof(float), hipMemcpyDefault, s));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------
 // slab boundary + kernel timer controls
 // ---------------------------------------------------------------------------
@@ -2753,6 +2852,7 @@ extern "C" int tnp_engine_set_owned_box(tnp_engine* e, const int32_t* lo3, const
 extern "C" int tnp_engine_set_eps(tnp_engine* e, float eps) {
   if (!e->has_net) { tnp_set_error("engine has no net"); return -1; }
   if (!(eps > 0.f)) { tnp_set_error("eps must be positive (got %g)", (double)eps); return -1; }
+  e->rows_valid = false;
   if (eps != e->net.eps_s) {
     e->net.eps_s = eps;
     e->masks_valid = false;  // first split planes at the new eps

@@ -845,9 +845,37 @@ k_fan_emit(int64_t F, const int32_t* __restrict__ frow, const int32_t* __restric
   }
 }
 
+// F6: the polygons themselves.  One thread per output index: it finds its row
+// by an upper-bound search in the offsets (F + 1 words, cache resident) and
+// copies one ordered member, so a wave's 64 stores are one contiguous 512 B
+// (a thread per row would scatter 3..20 stores each).  poff: the exclusive
+// scan of cnt over the F rows; poff[F] is written here.
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_poly_emit(int64_t n_idx, int64_t F, int64_t* __restrict__ poff, const int32_t* __restrict__ frow,
+            const int64_t* __restrict__ roff, const int32_t* __restrict__ ordv, int64_t* __restrict__ idx) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i == 0) poff[F] = n_idx;
+  if (i >= n_idx) return;
+  int64_t lo = 0, hi = F;  // the last row f in [0, F) with poff[f] <= i (poff[0] == 0)
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (poff[mid] <= i) lo = mid;
+    else hi = mid;
+  }
+  idx[i] = ordv[roff[frow[lo]] + (i - poff[lo])];
+}
+
 }  // namespace
 
 // ----------------------------------------------------------------------------
+int launch_poly_emit(int64_t n_idx, int64_t F, int64_t* poff, const int32_t* frow, const int64_t* roff,
+                     const int32_t* ordv, int64_t* idx, hipStream_t s) {
+  if (F <= 0) return 0;
+  hipLaunchKernelGGL(k_poly_emit, dim3(tnp_grid(n_idx)), dim3(TNP_BLOCK), 0, s, n_idx, F, poff, frow, roff, ordv,
+                     idx);
+  TNP_CHECK(hipGetLastError());
+  return 0;
+}
 int launch_face_count(int64_t V, const uint64_t* grid, const uint64_t* pos, const uint64_t* zero,
                       int K, int64_t* ctr2, hipStream_t s) {
   if (V <= 0) return 0;

@@ -308,6 +308,27 @@ class Engine:
             torch.cuda.current_stream(self.device).synchronize()  # (the stream of self._s)
         return tri, fc
 
+    def polygons(self, host: bool = False):
+        """The surface as convex polygons (tnp_engine_polygons): (offsets
+        [P + 1] int64, indices [offsets[-1]] int64 surface vertex ids, normals
+        [P, 3] float, the SDF gradient that ordered each polygon).  Polygon p
+        is indices[offsets[p]:offsets[p + 1]]; its fan, listed fan-position
+        major, is faces()' first tensor.  The rows of a faces() call on the
+        same complex are reused.  host=True: pinned host memory, as faces()."""
+        npoly, nidx = C.c_int64(), C.c_int64()
+        s = self._s
+        _hip.check(_hip.lib().tnp_engine_polygons(self.h, s, C.byref(npoly), C.byref(nidx)),
+                   "tnp_engine_polygons")
+        where = dict(device="cpu", pin_memory=True) if host else dict(device=self.device)
+        off = torch.empty(npoly.value + 1, dtype=torch.int64, **where)
+        idx = torch.empty(nidx.value, dtype=torch.int64, **where)
+        nrm = torch.empty(npoly.value, 3, **where)
+        _hip.check(_hip.lib().tnp_engine_polygons_export(self.h, _hip.ptr(off), _hip.ptr(idx), _hip.ptr(nrm), s),
+                   "tnp_engine_polygons_export")
+        if host:
+            torch.cuda.current_stream(self.device).synchronize()
+        return off, idx, nrm
+
     # -- the hot loop (subpoly.py:58-69) -------------------------------------
     def run_steps(self, stats: list = None, allreduce=None):
         """All hyperplane steps with empty steps skipped (they have no side

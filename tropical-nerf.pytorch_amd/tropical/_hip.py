@@ -45,6 +45,18 @@ class TnpStepStats(C.Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TnpPolygonStats(C.Structure):
+    _fields_ = [
+        ("n_polygons", C.c_int64), ("n_indices", C.c_int64), ("max_degree", C.c_int64),
+        ("n_vertices_used", C.c_int64), ("n_edges", C.c_int64), ("e_boundary", C.c_int64),
+        ("e_manifold", C.c_int64), ("e_nonmanifold", C.c_int64), ("e_misoriented", C.c_int64),
+        ("euler", C.c_int64), ("area", C.c_double), ("max_dev", C.c_float),
+    ]
+
+    def as_dict(self):
+        return {k: (float if k in ("area", "max_dev") else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
 # symbol -> (restype, argtypes); exactly the functions include/tropical_hip.h declares
 _VP, _I64, _I32, _F = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 _P64, _P32, _PU64 = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
@@ -89,6 +101,9 @@ SIGNATURES = {
     "tnp_engine_surface": (C.c_int, [_VP, _VP, _P64, _P64]),
     "tnp_engine_faces": (C.c_int, [_VP, _VP, _P64, _P64]),
     "tnp_engine_faces_export": (C.c_int, [_VP, _VP, _VP, _VP]),
+    "tnp_engine_polygons": (C.c_int, [_VP, _VP, _P64, _P64]),
+    "tnp_engine_polygons_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "tnp_polygon_report": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpPolygonStats), _VP, _VP, _VP]),
     "tnp_engine_set_owned": (C.c_int, [_VP, C.c_int, C.c_int]),
     "tnp_engine_set_xspan": (C.c_int, [_VP, C.c_int, C.c_int]),
     "tnp_engine_set_owned_box": (C.c_int, [_VP, _P32, _P32]),

@@ -25,7 +25,11 @@ dataset's own file is absent.  Extra flags: --weights PATH loads a
 state_dict from PATH instead of the cache location; --epochs overrides
 EPOCH (train.py:67); --layers / --hidden pick another net shape than the
 reference's 3 x 16 (any shape the library has kernels for, `supported_shapes`;
-model and mesh file names then carry a `_l{layers}h{hidden}` suffix).
+model and mesh file names then carry a `_l{layers}h{hidden}` suffix);
+--polygons also writes meshes/{d}/our_poly_mesh_{m}_{seed}.ply, the same
+surface as the convex polygons the triangles are fans of, and prints
+"Ours (polygons): P faces, mean degree D, edges E (boundary B, non-manifold
+N, misoriented M), euler X, max planarity dev Y" (tnp_polygon_report).
 """
 from __future__ import annotations
 
@@ -44,7 +48,7 @@ from tropical._buildid import CSRC
 from tropical.stanford.model import Net
 from tropical.utils.chamfer_distance import chamfer_distance, sample_surface_from_rays
 from tropical.utils.marching_cubes import marching_cubes_torch
-from tropical.utils.mesh import Mesh
+from tropical.utils.mesh import Mesh, PolygonMesh, polygon_report
 
 DIM = 3
 CANVAS_SIZE = 1.2
@@ -104,6 +108,8 @@ def parse_args(argv=None):
     p.add_argument("--mesh", default=None, help="training mesh (PLY) instead of the dataset's scan file")
     p.add_argument("--epochs", default=None, type=int, help="training epochs (default: the reference's EPOCH)")
     p.add_argument("--out", default="meshes", help="mesh output directory")
+    p.add_argument("--polygons", default=False, action="store_true",
+                   help="also write the surface as convex polygons (our_poly_mesh_*.ply) and report its edges")
     p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
     p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
     args = p.parse_args(argv)
@@ -198,14 +204,27 @@ def evaluate(net, our_mesh: Mesh, our_t: float, out_dir: str, tag: str, sizes=No
 BATCH_SIZE = 1000  # train.py:66
 
 
-def draw_canvas(net, force: bool):
-    """train.py:117-129 without the matplotlib canvas: subpoly, timed."""
+def draw_canvas(net, force: bool, polygons: bool = False):
+    """train.py:117-129 without the matplotlib canvas: subpoly, timed.  The
+    fifth value is the surface as a PolygonMesh (--polygons), else None."""
     t = time.time()
-    polygons, vertices, faces_with_indices = sp.subpoly(net, DIM, CANVAS_SIZE, force=force)
+    out = sp.subpoly(net, DIM, CANVAS_SIZE, force=force, polygons=polygons)
     torch.cuda.synchronize()
     our_t = time.time() - t
     print(f" take {our_t:.2f}")
-    return polygons, vertices, faces_with_indices, our_t
+    return out[0], out[1], out[2], our_t, (out[3] if polygons else None)
+
+
+def export_polygons(pmesh: PolygonMesh, verts, path: str):
+    """--polygons: the surface's convex polygons as a PLY over our_mesh's
+    (scaled) vertices `verts`, and one line on whether they close up."""
+    pm = PolygonMesh(verts, pmesh.offsets, pmesh.indices, pmesh.normals)
+    pm.export(path)
+    r = polygon_report(pm.vertices, pm.offsets, pm.indices)
+    mean = r["n_indices"] / max(r["n_polygons"], 1)
+    print(f"Ours (polygons): {r['n_polygons']} faces, mean degree {mean:.2f}, edges {r['n_edges']} "
+          f"(boundary {r['e_boundary']}, non-manifold {r['e_nonmanifold']}, misoriented {r['e_misoriented']}), "
+          f"euler {r['euler']}, max planarity dev {r['max_dev']:.3g}")
 
 
 def train_sdf(net, args, path: str):
@@ -233,7 +252,7 @@ def train_sdf(net, args, path: str):
                 if 5 * epochs > it:
                     print(" mesh calculation skipped.")
                     continue
-                result = draw_canvas(net, args.force)
+                result = draw_canvas(net, args.force, args.polygons)
     print("Finished training.", flush=True)
     if args.cache:
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -256,14 +275,14 @@ def main(argv=None):
         sd = torch.load(path, map_location=net.device(), weights_only=True)
         net.load_state_dict(sd)
         print(f"The pretrained model loaded from {path}")
-        polygons, vertices, faces_with_indices, our_t = draw_canvas(net, args.force)
+        polygons, vertices, faces_with_indices, our_t, pmesh = draw_canvas(net, args.force, args.polygons)
     else:
         if args.weights:
             raise SystemExit(f"--weights: no file at {path}")
         result = train_sdf(net, args, path)
         if result is None:
-            result = draw_canvas(net, args.force)
-        polygons, vertices, faces_with_indices, our_t = result
+            result = draw_canvas(net, args.force, args.polygons)
+        polygons, vertices, faces_with_indices, our_t, pmesh = result
 
     verts = vertices.cpu().numpy() / R
     our_mesh = Mesh(verts, np.asarray(faces_with_indices, dtype=np.int64))
@@ -271,6 +290,8 @@ def main(argv=None):
     out_dir = os.path.join(args.out, args.dataset)
     tag = f"{args.model_size}_{seed}{shape_suffix(args.layers, args.hidden)}"
     our_mesh.export(os.path.join(out_dir, f"our_mesh_{tag}.ply"))
+    if args.polygons:
+        export_polygons(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"))
     if not args.eval:
         return 0
     evaluate(net, our_mesh, our_t, out_dir, tag)

@@ -36,21 +36,30 @@ def _faces_to_numpy(tri: Tensor, faces: Tensor):
 
 @torch.no_grad()
 def subpoly(net, d: int, size: float, eps: float = 1e-4, force: bool = False,
-            stats: list = None) -> List:
+            stats: list = None, polygons: bool = False) -> List:
     """Skeleton -> all hyperplane steps -> surface -> faces (subpoly.py:23-86).
 
     Returns ``(faces float np F x 3 x 3, vertices V x 3 on net.device(),
     faces_with_indices int64 np F x 3)``; ``stats`` (optional list) receives
-    one counter dict per active step."""
+    one counter dict per active step.  ``polygons=True`` appends a fourth
+    value, the same surface as a ``PolygonMesh`` of convex polygons (the
+    triangles are their fans); the other three and the printed line are
+    unchanged."""
     if d != 3:
         raise NotImplementedError("d must be 3 (the reference's hash grid is 3-D)")
     eng = engine_for(net).set_curve(not force).set_eps(_eps(net, eps))
     eng.skeleton(unit=128, size=size)
     eng.run_steps(stats)
-    return _finish(eng, net)
+    return _finish(eng, net, polygons)
 
 
-def _finish(eng, net):
+def _polygon_mesh(eng, verts):
+    from .utils.mesh import PolygonMesh
+    off, idx, nrm = eng.polygons(host=True)  # (after faces(): the engine reuses its rows)
+    return PolygonMesh(verts.cpu().numpy(), off.numpy(), idx.numpy(), nrm.numpy())
+
+
+def _finish(eng, net, polygons=False):
     nV, nE = eng.sizes()
     print()
     print(f"# of vertices and edges = {nV}/{nE} => ", end="")
@@ -58,12 +67,13 @@ def _finish(eng, net):
     print(f"{sV}/{sE}", end=", ")
     if sV == 0:
         print("0 faces", end=", ")
-        return [], torch.zeros(0, dtype=torch.int64, device=eng.device), []
+        verts = torch.zeros(0, dtype=torch.int64, device=eng.device)
+        return ([], verts, [], _polygon_mesh(eng, verts)) if polygons else ([], verts, [])
     verts, _, _ = eng.export(edges=False)  # (the faces need no edge list)
     tri, fc = eng.faces(host=True)
     faces, fwi = _faces_to_numpy(tri, fc)
     print(f"{len(faces)} faces", end=", ")
-    return faces, verts, fwi
+    return (faces, verts, fwi, _polygon_mesh(eng, verts)) if polygons else (faces, verts, fwi)
 
 
 @torch.no_grad()
@@ -133,6 +143,19 @@ def extract_faces(vertices, edges, net, outputs=None, eps=None):
     eng.load(vertices, edges, outputs, keep_all=True)
     tri, fc = eng.faces(host=True)
     return _faces_to_numpy(tri, fc)
+
+
+def extract_polygons(vertices, edges, net, outputs=None, eps=None):
+    """The polygon counterpart of extract_faces: the same final rows
+    (subpoly.py:584-648) kept as convex polygons instead of fanned
+    (tensor_to_polygon_faces, subpoly.py:682-697).  Returns numpy ``offsets``
+    [P + 1], ``indices`` (ids into ``vertices``) and ``normals`` [P, 3]."""
+    if vertices.shape[0] == 0:
+        return np.zeros(1, np.int64), np.zeros(0, np.int64), np.zeros((0, 3), np.float32)
+    eng = engine_for(net).set_eps(_eps(net, eps))
+    eng.load(vertices, edges, outputs, keep_all=True)
+    off, idx, nrm = eng.polygons(host=True)
+    return off.numpy(), idx.numpy(), nrm.numpy()
 
 
 def get_hypercube(d, size):
