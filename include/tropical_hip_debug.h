@@ -33,6 +33,38 @@ int tnp_engine_faces_debug(tnp_engine* eng, float* d_scores, int64_t cap, int64_
 int tnp_engine_debug_set_lb_spin(tnp_engine* eng, int spin);
 int tnp_engine_debug_lb_recomputes(tnp_engine* eng, int64_t* n, int reset, void* stream);
 
+/* Debug: the single-pass count scan (csrc/scan.hip k_scan_lb) on its own,
+ * launched as the engine's steps launch it: through the engine's look-back
+ * buffer (chain 0), its launch epoch and its lb_spin.  d_out[i] = sum of
+ * d_in[0, i) (int32 counts, int64 offsets), *h_total (host) = the sum of all
+ * n; synchronises the stream.  A tile's status word holds 40 value bits:
+ * sums >= 2^40 are outside the scan's contract (counts of a complex never
+ * come near it) and are not checked. */
+int tnp_engine_debug_scan(tnp_engine* eng, const int32_t* d_in, int64_t n, int64_t* d_out,
+                          int64_t* h_total, void* stream);
+
+/* Debug: the launch epoch of look-back chain 0 / 1 (22 bits, advanced by
+ * every single-pass launch; csrc/engine.cpp lb_begin clears the records when
+ * it wraps).  *h_epoch (nullable): the epoch of the chain's last launch;
+ * set >= 0 then overwrites it -- the host field only, no device work, so the
+ * records in memory keep the epochs they were written with. */
+int tnp_engine_debug_lb_epoch(tnp_engine* eng, int chain, int64_t set, int64_t* h_epoch);
+
+/* Debug: the connecting-edge key sort (csrc/sort.hip sort_keys_lex) on n
+ * unique keys lo << nb | hi (zero above bit 2 nb) with run threshold R, as
+ * the connect phase calls it: private copies of the keys, a scratch of
+ * exactly the size the sort asks for.  d_out: the n keys ascending; d_keys is
+ * only read.  Synchronises the stream. */
+int tnp_debug_sort_keys_lex(const uint64_t* d_keys, int64_t n, int nb, int R, uint64_t* d_out,
+                            void* stream);
+
+/* Debug: the batched fill (csrc/scan.hip launch_fill) on k byte ranges in ONE
+ * call: range i is h_sizes[i] bytes at device pointer h_ptrs[i], set to the
+ * low byte of h_bytes[i] (host arrays).  Null and empty ranges are skipped;
+ * more non-empty ranges than one launch takes return -1. */
+int tnp_debug_fill(void* const* h_ptrs, const uint64_t* h_sizes, const uint32_t* h_bytes, int k,
+                   void* stream);
+
 /* Debug: the grouping kernel's LDS-record path (csrc/bucket.hip
  * k_bucket_group; on by default, TNP_LDS_RECORDS=0 at engine creation turns
  * it off): on = 0 sends every bucket's records through memory, as before. */

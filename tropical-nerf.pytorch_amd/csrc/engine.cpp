@@ -2947,6 +2947,43 @@ extern "C" int tnp_engine_debug_lb_recomputes(tnp_engine* e, int64_t* n, int res
   *n = (int64_t)v;
   return 0;
 }
+// the count scan on its own, as scan_counts runs it: chain 0 of the engine's
+// look-back buffer, its epoch and lb_spin; the total comes back to the host
+extern "C" int tnp_engine_debug_scan(tnp_engine* e, const int32_t* d_in, int64_t n, int64_t* d_out,
+                                     int64_t* h_total, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!e || !h_total || n < 0 || (n > 0 && (!d_in || !d_out))) {
+    tnp_set_error("tnp_engine_debug_scan: bad argument");
+    return -1;
+  }
+  TNP_CHECK(hipSetDevice(e->device));
+  int64_t* tot = nullptr;
+  TNP_CHECK(hipMalloc(&tot, sizeof(int64_t)));
+  TnpLB lb{};
+  int rc = (n > 0 && lb_begin(e, scan_tiles(n), s, &lb, 0, false)) ? -1 : 0;
+  if (rc == 0) rc = scan_i32_to_i64(d_in, d_out, n, tot, lb, s);
+  if (rc == 0 && hipMemcpyAsync(h_total, tot, sizeof(int64_t), hipMemcpyDeviceToHost, s) != hipSuccess) {
+    tnp_set_error("tnp_engine_debug_scan: total readback failed");
+    rc = -1;
+  }
+  if (hipStreamSynchronize(s) != hipSuccess && rc == 0) {
+    tnp_set_error("tnp_engine_debug_scan: stream synchronise failed");
+    rc = -1;
+  }
+  (void)hipFree(tot);
+  return rc;
+}
+// a look-back chain's launch epoch (lb_begin): read, and with set >= 0
+// overwritten -- the host field only, the records in memory stay
+extern "C" int tnp_engine_debug_lb_epoch(tnp_engine* e, int chain, int64_t set, int64_t* h_epoch) {
+  if (!e || chain < 0 || chain > 1 || set > 0x3FFFFF) {
+    tnp_set_error("tnp_engine_debug_lb_epoch: bad argument");
+    return -1;
+  }
+  if (h_epoch) *h_epoch = (int64_t)e->lb_epoch[chain];
+  if (set >= 0) e->lb_epoch[chain] = (uint32_t)set;
+  return 0;
+}
 
 // debugging aid: the gradient-descent fallback on arbitrary rows
 // (tropical_hip_debug.h; checked against the oracle's descent)

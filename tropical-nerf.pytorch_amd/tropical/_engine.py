@@ -258,6 +258,27 @@ class Engine:
                    "tnp_engine_debug_lb_recomputes")
         return n.value
 
+    def debug_scan(self, x: torch.Tensor):
+        """The count scan on its own (tnp_engine_debug_scan), through this
+        engine's look-back buffer, epoch and spin: (int64 exclusive prefix
+        sums of the int32 device tensor x, their total)."""
+        _hip.require_cuda(x, "debug_scan")
+        if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous():
+            raise ValueError("debug_scan: a contiguous 1-d int32 tensor")
+        out = torch.empty(x.shape[0], dtype=torch.int64, device=self.device)
+        tot = C.c_int64(-1)
+        _hip.check(_hip.lib().tnp_engine_debug_scan(self.h, _hip.ptr(x), x.shape[0], _hip.ptr(out),
+                                                    C.byref(tot), self._s), "tnp_engine_debug_scan")
+        return out, tot.value
+
+    def debug_lb_epoch(self, chain: int = 0, set: int = None) -> int:
+        """The launch epoch of look-back chain 0 / 1 (tnp_engine_debug_lb_epoch);
+        set != None then overwrites the host field (no device work)."""
+        n = C.c_int64()
+        _hip.check(_hip.lib().tnp_engine_debug_lb_epoch(self.h, int(chain), -1 if set is None else int(set),
+                                                        C.byref(n)), "tnp_engine_debug_lb_epoch")
+        return n.value
+
     # -- steps ---------------------------------------------------------------
     def active_planes(self, start: int = 0) -> int:
         m = C.c_uint64()

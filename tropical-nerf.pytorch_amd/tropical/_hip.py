@@ -123,6 +123,10 @@ SIGNATURES = {
     "tnp_engine_debug_set_lds_records": (C.c_int, [_VP, C.c_int]),
     "tnp_engine_debug_vertex_capacity": (C.c_int, [_VP, _P64, _P64]),
     "tnp_engine_debug_lb_recomputes": (C.c_int, [_VP, _P64, C.c_int, _VP]),
+    "tnp_engine_debug_scan": (C.c_int, [_VP, _VP, C.c_int64, _VP, _P64, _VP]),
+    "tnp_engine_debug_lb_epoch": (C.c_int, [_VP, C.c_int, C.c_int64, _P64]),
+    "tnp_debug_sort_keys_lex": (C.c_int, [_VP, C.c_int64, C.c_int, C.c_int, _VP, _VP]),
+    "tnp_debug_fill": (C.c_int, [C.POINTER(_VP), _PU64, C.POINTER(C.c_uint32), C.c_int, _VP]),
     "tnp_engine_kernel_timer": (C.c_int, [_VP, C.c_int, _VP, _P32]),
     "tnp_mc_count": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F, _VP, _VP, _VP, _P64, _P64, _VP]),
     "tnp_mc_emit": (C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _F, _VP, _VP, _VP, _VP, _VP, _VP]),
