@@ -489,6 +489,84 @@ int tnp_mt_emit(const float* d_vertices, const float* d_sdf, int64_t n_points, c
                 int64_t n_verts, int64_t n_one, float* d_verts, int64_t* d_interp, int64_t* d_faces,
                 int64_t* d_tet_idx, void* stream);
 
+/* ---- rasteriser (tropical/utils/render.py; csrc/render.hip) --------------
+ * Replaces the matplotlib plot_trisurf figures of tropical/stanford/visualize.py:13-67 (a CPU
+ * painter's algorithm) by an exact integer z-buffer rasteriser that also draws polygon boundaries.
+ *
+ * Input: the polygon soup of tnp_polygon_report -- d_xyz (V x 3 fp32), d_offsets (int64, P + 1),
+ * d_indices (int64); a triangle mesh is offsets 0, 3, 6, ...  Polygon p is drawn as its fan
+ * (p0, p[t+1], p[t+2]), t = 0 .. deg - 3; fan triangles are numbered polygon-major (triangle number
+ * T = sum of (deg - 2) over the polygons before p, plus t).  Checked on the device before anything is
+ * read through an id, with tnp_polygon_report's checks and its first-offender rule; V and the
+ * triangle count must be below 2^31.  P = 0 is valid: an all-background image.
+ *
+ * Projection (one thread per vertex, fp32, every operation rounded to nearest in the stated order):
+ *   d = p - center;  c_r = (right0 d0 + right1 d1) + right2 d2, likewise c_u (up), c_t (toward).
+ *   s = 1 (persp_dist D = 0, orthographic) or D / (D - c_t)  (D > 0, perspective).
+ *   sx = round((W / 2 + (scale s) c_r) 16),  sy = round((H / 2 - (scale s) c_u) 16)
+ *     in 1/16-pixel units, row 0 at the top (round: to nearest, ties to even).
+ *   sz = floor(((1 - q) / 2) 2^20) clamped to [0, 2^20 - 1]; a smaller sz is nearer the viewer.
+ *     Orthographic: q = c_t / h (h = depth_half).  Perspective: q is s mapped affinely so that
+ *     c_t = -h, +h give -1, +1, evaluated as q = (c_t D - h h) / (h (D - c_t)); s is linear in
+ *     screen space, so plain interpolation of sz over a triangle is exact.
+ *   A vertex is FLAGGED when |sx| or |sy| exceeds 2^18 (or is not a number), q lies outside
+ *   [-1, 1], or, under perspective, c_t >= D.  Every polygon that uses a flagged vertex is dropped
+ *   and counted; there is no clipping stage.  d_screen (V x 3 int32, may be NULL) receives
+ *   (sx, sy, sz), and (0, 0, -1) for a flagged vertex.
+ *
+ * Coverage and depth are integer: the result depends neither on launch order nor on rounding.
+ *   e(a, b, p) = (b.x - a.x)(p.y - a.y) - (b.y - a.y)(p.x - a.x) in int64.
+ *   A2 = e(v0, v1, v2); A2 < 0: v1 and v2 are swapped; A2 = 0: the triangle draws nothing.
+ *   Pixel (i, j) (column i, row j) has centre p = (16 i + 8, 16 j + 8).
+ *   w0 = e(v1, v2, p), w1 = e(v2, v0, p), w2 = e(v0, v1, p).  The pixel is covered iff for every k
+ *   w_k > 0, or w_k = 0 and the edge a -> b of w_k, d = b - a, owns its points: d.y > 0, or
+ *   d.y = 0 and d.x < 0.  (Two triangles sharing an edge never both cover, or both miss, a centre
+ *   on it.)  Depth z = (w0 z0 + w1 z1 + w2 z2) // A2 (every product stays below 2^60).
+ *   Visibility: one 64-bit atomic minimum of (z << 32) | T per covered pixel, background all ones:
+ *   the nearest wins, ties go to the lowest triangle number; no back-face culling.
+ *   Two coverage paths with identical results: a triangle whose bounding box of pixel centres,
+ *   clamped to the image, is at most TNP_RENDER_SMALL_MAX pixels wide and high is drawn by one
+ *   thread; the others are compacted into a list (scan.hip) and drawn a workgroup per triangle,
+ *   16 x 16-pixel tiles of the clamped box, a tile skipped when an edge excludes all of it.
+ *
+ * Resolve (one thread per pixel): d_prim (int32 H x W) the winning polygon id, -1 background;
+ *   d_tri (int32 H x W, may be NULL) the winning triangle number T, -1 background; d_edge (uint8
+ *   H x W, may be NULL) 1 iff the pixel centre lies within edge_half_width (1/16 px, 0 .. 256) of a
+ *   polygon-boundary edge a -> b of the winning triangle: |e(a, b, p)| <= edge_half_width
+ *   isqrt(|b - a|^2), isqrt the exact integer square root.  The boundary edges of fan triangle t
+ *   are (p[t+1], p[t+2]) always, (p0, p1) when t = 0 and (p[deg-1], p0) when t = deg - 3; fan
+ *   diagonals are never edges.  Background pixels have edge 0.
+ * h_stats (host): polygons drawn / dropped (a flagged vertex) / degenerate (not dropped, every fan
+ *   triangle has A2 = 0), fan triangles, those sent down the workgroup path, pixels covered.
+ * Synchronises `stream`. */
+#define TNP_RENDER_SMALL_MAX 8
+typedef struct tnp_render_view {
+  float right[3], up[3], toward[3]; /* rotation rows; toward points at the viewer */
+  float center[3];
+  float scale;        /* pixels per world unit */
+  float persp_dist;   /* D; 0: orthographic */
+  float depth_half;   /* h > 0 */
+  int32_t width, height; /* the raster, 1 .. 8192 each */
+} tnp_render_view;
+typedef struct tnp_render_stats {
+  int64_t n_polygons, n_drawn, n_dropped, n_degenerate;
+  int64_t n_triangles, n_large, pixels_covered;
+} tnp_render_stats;
+int tnp_render_raster(const float* d_xyz, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
+                      int64_t P, const tnp_render_view* view, int32_t edge_half_width, int32_t* d_screen,
+                      int32_t* d_prim, int32_t* d_tri, uint8_t* d_edge, tnp_render_stats* h_stats,
+                      void* stream);
+
+/* Shade: d_prim / d_edge (nullable) of a width x height raster -> RGBA8 (height / ss) x (width / ss),
+ * ss in {1, 2, 4} dividing both.  Per raster pixel: background (id outside [0, P)) is (0, 0, 0, 0);
+ * an edge pixel takes edge_rgba (4 bytes, host); else (lut[k], 255) with d_lut 256 x 3 uint8 and
+ * k = clamp(floor((v - vmin) / (vmax - vmin) 255 + 0.5), 0, 255) in fp32, each operation rounded to
+ * nearest in that order, v = d_value[id] (P floats; not a number: k = 0); vmax > vmin.  Each
+ * ss x ss block is then averaged per channel as (sum + n / 2) // n, n = ss ss, in integers. */
+int tnp_render_shade(const int32_t* d_prim, const uint8_t* d_edge, int32_t width, int32_t height,
+                     const float* d_value, int64_t P, float vmin, float vmax, const uint8_t* d_lut,
+                     const uint8_t* edge_rgba, int32_t ss, uint8_t* d_rgba, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,12 @@ int tnp_debug_buf_growth(int64_t have_bytes, int64_t request_bytes, int64_t memb
 int tnp_debug_descend(const tnp_net* net, const float* d_ends, float* d_x, const int32_t* d_plane, int64_t n,
                       int idx, float eps, int iters, float* d_d0, float* d_d1, int per_thread, void* stream);
 
+/* Debug: which coverage path tnp_render_raster takes (csrc/render.hip).  0 (default): by the
+ * bounding box against TNP_RENDER_SMALL_MAX; 1: every triangle by one thread; 2: every triangle
+ * by a workgroup.  The buffers must not depend on it.  Process-wide; returns the previous mode,
+ * -1 for a mode outside 0 .. 2. */
+int tnp_debug_render_path(int mode);
+
 #ifdef __cplusplus
 }
 #endif

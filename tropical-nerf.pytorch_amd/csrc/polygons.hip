@@ -2,7 +2,7 @@
 // (include/tropical_hip.h has the definitions).  The engine is not involved:
 // scratch is allocated per call on the caller's stream and freed.
 //
-//   k_poly_offsets  per polygon: the offsets are checked, degrees written
+//   k_soup_offsets  per polygon: the offsets are checked, degrees written
 //   k_poly_edges    per index: ids checked, one directed-edge key and one
 //                   used-vertex flag written (stores only -- nothing is loaded
 //                   through an id here)
@@ -19,48 +19,15 @@
 
 #include "faces.h"
 #include "kernels.h"
+#include "soup_check.h"
 #include "step.h"
 
 namespace {
 
 // counter block (int64 words)
 enum { PC_ERR, PC_NIDX, PC_MAXDEG, PC_VUSED, PC_EDGES, PC_BOUND, PC_MANI, PC_NONM, PC_MISO, PC_DEV, PC_AREA, PC_N };
-// error word: (position << 3) | code, the smallest wins; PE_NONE: no error
-enum { PE_OFF0, PE_DECR, PE_SHORT, PE_LONG, PE_ID, PE_EQUAL };
-constexpr unsigned long long PE_NONE = ~0ull;
-
-__device__ __forceinline__ void poly_fail(int64_t* ctr, int64_t at, int code) {
-  atomicMin(reinterpret_cast<unsigned long long*>(ctr + PC_ERR), ((unsigned long long)at << 3) | (unsigned)code);
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_poly_offsets(const int64_t* __restrict__ off, int64_t P, int64_t* __restrict__ ctr, int32_t* __restrict__ deg) {
-  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (p == 0) {
-    if (off[0] != 0) poly_fail(ctr, 0, PE_OFF0);
-    ctr[PC_NIDX] = off[P];
-  }
-  if (p >= P) return;
-  const int64_t a = off[p], b = off[p + 1];
-  int d = 0;
-  if (b < a) poly_fail(ctr, p, PE_DECR);
-  else if (b - a < 3) poly_fail(ctr, p, PE_SHORT);
-  else if (b - a > 0x7fffffff) poly_fail(ctr, p, PE_LONG);
-  else d = (int)(b - a);
-  deg[p] = d;
-}
-
-// the polygon of index position i: the last p in [0, P) with off[p] <= i
-// (checked offsets: off[0] == 0, increasing, off[P] > i)
-__device__ __forceinline__ int64_t polygon_of(const int64_t* __restrict__ off, int64_t P, int64_t i) {
-  int64_t lo = 0, hi = P;
-  while (hi - lo > 1) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (off[mid] <= i) lo = mid;
-    else hi = mid;
-  }
-  return lo;
-}
+// (the error word, the offsets kernel and the id check are soup_check.h's: PC_ERR / PC_NIDX are its two words)
+static_assert(PC_ERR == SOUP_ERR && PC_NIDX == SOUP_NIDX, "counter layout");
 
 // one key per index position i: the edge from idx[i] to the next id of its
 // polygon (cyclic), (min << 32) | (max << 1) | (from > to)
@@ -69,17 +36,12 @@ k_poly_edges(const int64_t* __restrict__ off, int64_t P, const int64_t* __restri
              int64_t* __restrict__ ctr, uint8_t* __restrict__ used, uint64_t* __restrict__ keys) {
   const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
   if (i >= n) return;
-  const int64_t p = polygon_of(off, P, i);
-  const int64_t j = i + 1 == off[p + 1] ? off[p] : i + 1;
-  const int64_t a = idx[i], b = idx[j];
-  const bool a_ok = a >= 0 && a < V, b_ok = b >= 0 && b < V;  // (b is reported by its own thread)
+  int64_t a, b;
+  bool b_ok;
   uint64_t key = 0;
-  if (!a_ok) {
-    poly_fail(ctr, i, PE_ID);
-  } else {
+  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok)) {
     used[a] = 1;
     if (b_ok) {
-      if (a == b) poly_fail(ctr, i, PE_EQUAL);
       const uint64_t lo = (uint64_t)(a < b ? a : b), hi = (uint64_t)(a < b ? b : a);
       key = (lo << 32) | (hi << 1) | (a > b ? 1u : 0u);
     }
@@ -140,7 +102,7 @@ k_poly_geom(const float* __restrict__ xyz, const int64_t* __restrict__ off, cons
   __shared__ double lds_a[TNP_WAVES];
   __shared__ float lds_d[TNP_WAVES];
   if (__hip_atomic_load(reinterpret_cast<unsigned long long*>(ctr + PC_ERR), __ATOMIC_RELAXED,
-                        __HIP_MEMORY_SCOPE_AGENT) != PE_NONE)
+                        __HIP_MEMORY_SCOPE_AGENT) != SOUP_NONE)
     return;  // (every thread: a failed check)
   const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
   float A = 0.f, D = 0.f;
@@ -212,7 +174,7 @@ __global__ void __launch_bounds__(TNP_BLOCK)
 k_area_total(const double* __restrict__ partial, int64_t n, int64_t* __restrict__ ctr) {
   __shared__ double lds[TNP_WAVES];
   if (__hip_atomic_load(reinterpret_cast<unsigned long long*>(ctr + PC_ERR), __ATOMIC_RELAXED,
-                        __HIP_MEMORY_SCOPE_AGENT) != PE_NONE)
+                        __HIP_MEMORY_SCOPE_AGENT) != SOUP_NONE)
     return;
   double t = 0.0;
   for (int64_t i = threadIdx.x; i < n; i += TNP_BLOCK) t += partial[i];
@@ -247,39 +209,6 @@ struct Scratch {
   }
 };
 
-// the failed check of error word w as tnp_last_error(); the offending values
-// are read back from positions the checks have shown to be inside the arrays
-int poly_report_error(unsigned long long w, const int64_t* d_off, const int64_t* d_idx, int64_t V, hipStream_t s) {
-  const long long at = (long long)(w >> 3);
-  const int code = (int)(w & 7);
-  int64_t v[2] = {0, 0};
-  if (code <= PE_LONG)
-    TNP_CHECK(hipMemcpyAsync(v, d_off + at, (code == PE_OFF0 ? 1 : 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  else
-    TNP_CHECK(hipMemcpyAsync(v, d_idx + at, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  switch (code) {
-    case PE_OFF0: tnp_set_error("polygon_report: offsets[0] = %lld, not 0", (long long)v[0]); break;
-    case PE_DECR:
-      tnp_set_error("polygon_report: offsets decrease at polygon %lld (offsets[%lld] = %lld > offsets[%lld] = %lld)",
-                    at, at, (long long)v[0], at + 1, (long long)v[1]);
-      break;
-    case PE_SHORT:
-      tnp_set_error("polygon_report: polygon %lld has %lld ids, fewer than 3", at, (long long)(v[1] - v[0]));
-      break;
-    case PE_LONG:
-      tnp_set_error("polygon_report: polygon %lld has %lld ids, more than 2^31 - 1", at, (long long)(v[1] - v[0]));
-      break;
-    case PE_ID:
-      tnp_set_error("polygon_report: indices[%lld] = %lld is outside [0, %lld)", at, (long long)v[0], (long long)V);
-      break;
-    default:
-      tnp_set_error("polygon_report: indices[%lld] = %lld and the next id of its polygon are equal", at,
-                    (long long)v[0]);
-  }
-  return -1;
-}
-
 }  // namespace
 
 extern "C" int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
@@ -300,14 +229,14 @@ extern "C" int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* 
   if (!ctr || !deg) return -1;
   int64_t h[PC_N];
   for (int i = 0; i < PC_N; ++i) h[i] = 0;
-  h[PC_ERR] = (int64_t)PE_NONE;
+  h[PC_ERR] = (int64_t)SOUP_NONE;
   TNP_CHECK(hipMemcpyAsync(ctr, h, sizeof(h), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_poly_offsets, dim3(tnp_grid(P)), dim3(TNP_BLOCK), 0, s, d_offsets, P, ctr, deg);
+  hipLaunchKernelGGL(k_soup_offsets, dim3(tnp_grid(P)), dim3(TNP_BLOCK), 0, s, d_offsets, P, ctr, deg);
   TNP_CHECK(hipGetLastError());
   TNP_CHECK(hipMemcpyAsync(h, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[PC_ERR] != PE_NONE)
-    return poly_report_error((unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
+  if ((unsigned long long)h[PC_ERR] != SOUP_NONE)
+    return soup_report_error("polygon_report", (unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
   const int64_t n = h[PC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
 
   int bits = 1;
@@ -337,8 +266,8 @@ extern "C" int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* 
   TNP_CHECK(hipGetLastError());
   TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[PC_ERR] != PE_NONE)
-    return poly_report_error((unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
+  if ((unsigned long long)h[PC_ERR] != SOUP_NONE)
+    return soup_report_error("polygon_report", (unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
   h_out->n_polygons = P;
   h_out->n_indices = n;
   h_out->max_degree = h[PC_MAXDEG];

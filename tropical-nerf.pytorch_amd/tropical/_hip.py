@@ -57,6 +57,22 @@ class TnpPolygonStats(C.Structure):
         return {k: (float if k in ("area", "max_dev") else int)(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TnpRenderView(C.Structure):
+    _fields_ = [
+        ("right", C.c_float * 3), ("up", C.c_float * 3), ("toward", C.c_float * 3), ("center", C.c_float * 3),
+        ("scale", C.c_float), ("persp_dist", C.c_float), ("depth_half", C.c_float),
+        ("width", C.c_int32), ("height", C.c_int32),
+    ]
+
+
+class TnpRenderStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_polygons", "n_drawn", "n_dropped", "n_degenerate", "n_triangles",
+                                          "n_large", "pixels_covered")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 # symbol -> (restype, argtypes); exactly the functions include/tropical_hip.h declares
 _VP, _I64, _I32, _F = C.c_void_p, C.c_int64, C.c_int32, C.c_float
 _P64, _P32, _PU64 = C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_uint64)
@@ -104,6 +120,11 @@ SIGNATURES = {
     "tnp_engine_polygons": (C.c_int, [_VP, _VP, _P64, _P64]),
     "tnp_engine_polygons_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "tnp_polygon_report": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpPolygonStats), _VP, _VP, _VP]),
+    "tnp_render_raster": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpRenderView), _I32, _VP, _VP, _VP, _VP,
+                                    C.POINTER(TnpRenderStats), _VP]),
+    "tnp_render_shade": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I64, _F, _F, _VP, C.POINTER(C.c_uint8), _I32, _VP,
+                                   _VP]),
+    "tnp_debug_render_path": (C.c_int, [C.c_int]),
     "tnp_engine_set_owned": (C.c_int, [_VP, C.c_int, C.c_int]),
     "tnp_engine_set_xspan": (C.c_int, [_VP, C.c_int, C.c_int]),
     "tnp_engine_set_owned_box": (C.c_int, [_VP, _P32, _P32]),
