@@ -270,6 +270,68 @@ typedef struct tnp_polygon_stats {
 int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
                        int64_t P, tnp_polygon_stats* h_out, float* d_area, float* d_dev, void* stream);
 
+/* Connected components and boundary loops of a polygon soup (csrc/topology.hip), the soup as
+ * tnp_polygon_report takes it, with its checks, its first-offender rule and its message texts
+ * (prefix "topology"); V and P must be below 2^31.  P = 0: 0 components, 0 loops.
+ *
+ * Components.  Two polygons are adjacent when they share an undirected edge (connect = 0) or a
+ * vertex id (connect = 1); a component is a class of the transitive closure, so all users of a
+ * non-manifold edge are one component, and two closed shells that touch at one vertex are two
+ * components under connect = 0 and one under connect = 1.  Components are numbered by ascending
+ * smallest polygon id: label[p] in [0, C) is a function of the input alone.  Every undirected edge
+ * lies in exactly one component in both modes.  One tnp_component row per component:
+ *  - first_polygon (its smallest polygon id), n_polygons, n_indices (the sum of its degrees);
+ *  - n_vertices: the distinct ids its polygons use;
+ *  - n_edges, e_boundary, e_manifold, e_nonmanifold, e_misoriented: tnp_polygon_report's classes
+ *    over the component's edges (each column sums to the report's total);
+ *  - euler = n_vertices - n_edges + n_polygons;
+ *  - area: the sum in double of tnp_polygon_report's fp32 per-polygon areas (the same bits per polygon);
+ *  - volume: with the fp32 coordinates converted to double, D = sum over the polygons and their fan
+ *    triangles (p0, p[t+1], p[t+2]) of p0 . (p[t+1] x p[t+2]), each product and sum rounded once
+ *    (p0x (p1y p2z - p1z p2y) + p0y (p1z p2x - p1x p2z) + p0z (p1x p2y - p1y p2x), left to right);
+ *    volume = D / 6: the signed enclosed volume when the component is closed and consistently
+ *    oriented (e_boundary = e_nonmanifold = e_misoriented = 0), outward winding positive;
+ *  - lo, hi: the fp32 bounding box of the vertices its polygons use.
+ *  A polygon's fan triangles are added left to right; the polygons' areas and determinant sums
+ *  are reduced in a shape fixed by the input: the polygons in (label, polygon id) order,
+ *  cut into pieces at the multiples of 256 of that order and at the component boundaries; a piece
+ *  that is a whole 256-block is summed by a fixed tree, any other piece left to right; a component's
+ *  pieces, in order, by 64 strided partial sums and a fixed tree.  The same bits on every call.
+ *
+ * Boundary loops.  The boundary graph has the vertex ids as nodes and the edges used exactly once
+ * as edges; a loop is a connected component of it with at least one edge.  Loops are numbered by
+ * ascending smallest vertex id.  One tnp_boundary_loop row per loop:
+ *  - first_vertex (its smallest vertex id), n_edges, n_vertices;
+ *  - simple: 1 iff every vertex of the loop has exactly two boundary edges;
+ *  - component: the label of the polygon that owns the loop's smallest edge key (min << 32) | max;
+ *  - length: each edge's length in double from the fp32 coordinates (differences, squares, their sum
+ *    left to right, sqrt), summed over the loop's edges in ascending edge key in the shape above.
+ *
+ * build labels the soup, keeps the three tables in the handle (replacing those of an earlier build)
+ * and returns the counts; export copies them to device memory (label int32 [P], C rows, L rows; any
+ * may be NULL), asynchronously on `stream`.  build synchronises `stream`. */
+typedef struct tnp_component {
+  int64_t first_polygon, n_polygons, n_indices, n_vertices;
+  int64_t n_edges, e_boundary, e_manifold, e_nonmanifold, e_misoriented;
+  int64_t euler;
+  double area, volume;
+  float lo[3], hi[3];
+} tnp_component;
+typedef struct tnp_boundary_loop {
+  int64_t first_vertex, n_edges, n_vertices;
+  int64_t component;
+  double length;
+  int32_t simple, reserved; /* reserved: 0 */
+} tnp_boundary_loop;
+typedef struct tnp_topology tnp_topology;
+int tnp_topology_create(tnp_topology** out, int device);
+void tnp_topology_destroy(tnp_topology* t);
+int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V, const int64_t* d_offsets,
+                       const int64_t* d_indices, int64_t P, int connect, int64_t* n_components,
+                       int64_t* n_loops, void* stream);
+int tnp_topology_export(tnp_topology* t, int32_t* d_label, tnp_component* d_components,
+                        tnp_boundary_loop* d_loops, void* stream);
+
 /* 1: subpoly_(..., force=False) -- the curve-approximation branch
  * (subpoly.py:120-177, 201-207; geometry.py:24-138, 259-299;
  * subpoly_debug.py:121-165, 234-271): new vertices of non-axis-aligned split

@@ -102,6 +102,14 @@ int tnp_debug_descend(const tnp_net* net, const float* d_ends, float* d_x, const
  * -1 for a mode outside 0 .. 2. */
 int tnp_debug_render_path(int mode);
 
+/* Debug: stage times of tnp_topology_build (csrc/topology.hip).  enable != 0: later builds on this
+ * handle record an event between their stages.  ms != NULL: the milliseconds of the last timed
+ * build's stages (at most n of them), in the order check_edges, edge_sort, label_polygons,
+ * label_boundary, tables_alloc, component_counts, vertex_sort, polygon_order, geometry, loops.
+ * Returns the number of stages (TNP_TOPOLOGY_STAGES), -1 on error. */
+#define TNP_TOPOLOGY_STAGES 10
+int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n);
+
 #ifdef __cplusplus
 }
 #endif

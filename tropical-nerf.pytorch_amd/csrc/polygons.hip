@@ -19,6 +19,7 @@
 
 #include "faces.h"
 #include "kernels.h"
+#include "poly_geom.h"
 #include "soup_check.h"
 #include "step.h"
 
@@ -81,20 +82,11 @@ k_edge_runs(const uint64_t* __restrict__ k, int64_t n, int64_t* __restrict__ ctr
               (unsigned long long)lds[threadIdx.x]);
 }
 
-// sum += x with the rounding error carried in comp (no fast-math: the
-// compiler keeps the order)
-__device__ __forceinline__ void kahan_add(float& sum, float& comp, float x) {
-  const float y = x - comp;
-  const float t = sum + y;
-  comp = (t - sum) - y;
-  sum = t;
-}
-
 // fp32 Newell about the members' mean c: N = 1/2 sum (p_i - c) x (p_i+1 - c),
 // area |N|, dev = max |(p_i - c) . N| / |N| (0 when |N| = 0).  One thread per
-// polygon walks its members in order (degrees are 3..20 on the extracted
-// surfaces; any degree works).  The areas leave the workgroup as one double
-// partial, reduced in a fixed order; dev >= 0, so its bits order as integers.
+// polygon walks its members in order (poly_geom.h newell_area).  The areas
+// leave the workgroup as one double partial, reduced in a fixed order;
+// dev >= 0, so its bits order as integers.
 __global__ void __launch_bounds__(TNP_BLOCK)
 k_poly_geom(const float* __restrict__ xyz, const int64_t* __restrict__ off, const int64_t* __restrict__ idx,
             int64_t P, int64_t* __restrict__ ctr, float* __restrict__ area, float* __restrict__ dev,
@@ -108,30 +100,8 @@ k_poly_geom(const float* __restrict__ xyz, const int64_t* __restrict__ off, cons
   float A = 0.f, D = 0.f;
   if (p < P) {
     const int64_t a = off[p], b = off[p + 1];
-    // both sums are compensated (Kahan): a plain fp32 running sum over a
-    // 200-gon's members drifts by several ulp of the result, more than the
-    // formula's own rounding
-    float c[3] = {0.f, 0.f, 0.f}, cc[3] = {0.f, 0.f, 0.f};
-    for (int64_t i = a; i < b; ++i) {
-      const float* q = xyz + 3 * idx[i];
-#pragma unroll
-      for (int k = 0; k < 3; ++k) kahan_add(c[k], cc[k], q[k]);
-    }
-    const float m = (float)(b - a);
-    c[0] /= m, c[1] /= m, c[2] /= m;
-    float N[3] = {0.f, 0.f, 0.f}, Nc[3] = {0.f, 0.f, 0.f};
-    const float* q0 = xyz + 3 * idx[b - 1];
-    float u[3] = {q0[0] - c[0], q0[1] - c[1], q0[2] - c[2]};  // the edge (last, first) comes first
-    for (int64_t i = a; i < b; ++i) {
-      const float* q = xyz + 3 * idx[i];
-      const float v[3] = {q[0] - c[0], q[1] - c[1], q[2] - c[2]};
-      kahan_add(N[0], Nc[0], u[1] * v[2] - u[2] * v[1]);
-      kahan_add(N[1], Nc[1], u[2] * v[0] - u[0] * v[2]);
-      kahan_add(N[2], Nc[2], u[0] * v[1] - u[1] * v[0]);
-      u[0] = v[0], u[1] = v[1], u[2] = v[2];
-    }
-    N[0] *= 0.5f, N[1] *= 0.5f, N[2] *= 0.5f;
-    A = sqrtf(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]);
+    float c[3], N[3];
+    A = newell_area(xyz, idx, a, b, c, N);
     if (A > 0.f) {
       for (int64_t i = a; i < b; ++i) {
         const float* q = xyz + 3 * idx[i];

@@ -1,8 +1,9 @@
 // The checks every entry point that takes a polygon soup (d_offsets int64
 // [P + 1], d_indices int64) makes on the device before anything is read
-// through an id -- tnp_polygon_report (polygons.hip) and tnp_render_raster
-// (render.hip) share them, so both refuse the same input and name the same
-// first offender.  Included by those two files only (anonymous namespace).
+// through an id -- tnp_polygon_report (polygons.hip), tnp_render_raster
+// (render.hip) and tnp_topology_build (topology.hip) share them, so all
+// refuse the same input and name the same first offender.  Included by those
+// three files only (anonymous namespace).
 //
 // ctr[SOUP_ERR]: the error word, (position << 3) | code under atomicMin, so
 // the smallest position wins; SOUP_NONE: no error.  ctr[SOUP_NIDX] = off[P].

@@ -388,6 +388,10 @@ int sort_pairs_u32(uint32_t* ka, uint32_t* kb, int32_t* va, int32_t* vb, int64_t
                    void* scratch, size_t scratch_bytes, uint32_t** ko, int32_t** vo, hipStream_t s);
 int sort_keys_u64(uint64_t* a, uint64_t* b, int64_t n, int bits, void* scratch, size_t scratch_bytes,
                   uint64_t** out, hipStream_t s);
+// the same for (u64 key, i32 value) pairs (topology.hip: edge key, owning polygon)
+size_t sort_pairs_u64_scratch_bytes(int64_t n, int bits);
+int sort_pairs_u64(uint64_t* ka, uint64_t* kb, int32_t* va, int32_t* vb, int64_t n, int bits,
+                   void* scratch, size_t scratch_bytes, uint64_t** ko, int32_t** vo, hipStream_t s);
 // connecting-edge keys lo << nb | hi in lexicographic order: the lo half
 // radix-sorted, then each run of equal lo ordered by hi (runs of <= R keys
 // in one pass, longer ones one workgroup each); R <= 0 or n within the merge

@@ -1,0 +1,906 @@
+// tnp_topology_*: connected components and boundary loops of a polygon soup
+// (include/tropical_hip.h has the definitions).  The engine is not involved:
+// scratch is allocated per build on the caller's stream and freed; the handle
+// keeps the three result tables.
+//
+//   k_soup_offsets    (soup_check.h) the offsets are checked
+//   k_topo_edges      per index: ids checked, one directed-edge key (the
+//                     report's) and its polygon written -- nothing is loaded
+//                     through an id
+//   sort_pairs_u64    (key, polygon) on the bits the ids need
+//   k_union_edges     lock-free union-find over the polygons: every use of an
+//                     undirected edge is united with the use before it in the
+//                     sorted run (the same classes as uniting each with the
+//                     run's first, and no walk back to find it).  connect = 1:
+//                     k_vertex_owner (the smallest polygon at each vertex) and
+//                     k_union_vertices instead
+//   k_boundary_union  the same union-find over the vertices, one union per
+//                     edge used once; boundary degrees
+//   k_flag_roots, scan_i32_to_i64 (x 2)   hooks go to the smaller id, so a
+//                     root is its class's smallest member: the exclusive scan
+//                     of the root flags ranks the classes canonically
+//   k_labels          the flatten pass: label[p] = rank[find(p)]
+//   k_comp_polys      per polygon: degree and box into its component (integer
+//                     atomics, one per wave and label present in it), fp32
+//                     area and double fan determinant stored
+//   k_edge_stats      per sorted run: the report's five classes per component
+//   k_vertex_keys, sort_keys_u64, k_key_runs     distinct (label, vertex)
+//   k_poly_keys, sort_keys_u64, k_seg_starts     the polygons in (label, p)
+//                     order; a component's segment gives n_polygons
+//   k_seg_pieces, k_seg_final   the doubles, reduced in a shape fixed by the
+//                     input (no float atomics)
+//   k_loop_verts, k_loop_keys, sort_keys_u64, k_seg_starts, k_seg_pieces,
+//   k_seg_final       the loops' counts and lengths the same way
+//   k_comp_rows, k_loop_rows    the tables
+// The number of launches is fixed (it does not depend on the graph), and no
+// kernel waits for another workgroup: a failed hook is retried from the new
+// root.
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../../include/tropical_hip_debug.h"
+#include "kernels.h"
+#include "poly_geom.h"
+#include "soup_check.h"
+#include "step.h"
+
+struct tnp_topology {
+  int device = 0;
+  int32_t* label = nullptr;
+  tnp_component* comps = nullptr;
+  tnp_boundary_loop* loops = nullptr;
+  int64_t P = 0, C = 0, L = 0;
+  bool timed = false;
+  int n_ms = 0;
+  double ms[TNP_TOPOLOGY_STAGES] = {};
+};
+
+namespace {
+
+// counter block (int64 words); the first two are soup_check.h's
+enum { TC_ERR, TC_NIDX, TC_C, TC_L, TC_B, TC_N };
+static_assert(TC_ERR == SOUP_ERR && TC_NIDX == SOUP_NIDX, "counter layout");
+// per-component int64 columns, per-loop int64 columns
+enum { CK_FIRST, CK_NIDX, CK_NVERT, CK_EDGES, CK_BOUND, CK_MANI, CK_NONM, CK_MISO, CK_N };
+enum { LK_FIRST, LK_NVERT, LK_NONSIMPLE, LK_N };
+constexpr int SEG = TNP_BLOCK;  // positions per piece block of the segmented sums
+
+__device__ __forceinline__ int ld_i32(const int* p) {
+  return __hip_atomic_load(const_cast<int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// Union-find over ids [0, n): parent[x] <= x always (a root is only ever
+// hooked under a smaller root), so every chain ends and a root is the
+// smallest member of its class.
+// find with path halving: a non-root's parent is replaced by its grandparent.
+// Any ancestor is a valid parent and a non-root never becomes a root again,
+// so the plain relaxed stores race harmlessly with each other and cannot
+// collide with a hook (the CAS below expects parent[x] == x).
+__device__ __forceinline__ int uf_find(int* parent, int x) {
+  while (true) {
+    const int p = ld_i32(parent + x);
+    if (p == x) return x;
+    const int g = ld_i32(parent + p);
+    if (g == p) return p;
+    __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    x = g;
+  }
+}
+
+// hook the larger root under the smaller; a lost race (the larger is no
+// longer a root) is retried from its new root -- no thread waits for another
+__device__ __forceinline__ void uf_union(int* parent, int a, int b) {
+  a = uf_find(parent, a);
+  b = uf_find(parent, b);
+  while (a != b) {
+    if (a < b) {
+      const int t = a;
+      a = b;
+      b = t;
+    }
+    const int old = atomicCAS(parent + a, a, b);
+    if (old == a) return;
+    a = uf_find(parent, old);
+    b = uf_find(parent, b);
+  }
+}
+
+// Integer adds into per-class counters.  The active lanes of a wave are taken
+// class by class: f(in, c0, leader) runs once per distinct class c0 among
+// them, `in` marking its lanes, and reduces over them before one lane issues
+// the atomic.  One giant component is the common case: one round and one
+// atomic per wave, where every lane would otherwise hit the same word; a wave
+// that also holds a few floaters takes a round for each.  The loop is
+// wave-uniform; every lane of the wave must call it.
+template <class F>
+__device__ __forceinline__ void wave_classes(bool active, int c, F&& f) {
+  uint64_t todo = __ballot(active);
+  while (todo) {
+    const int leader = __builtin_ctzll(todo);
+    const int c0 = __shfl(c, leader, 64);
+    const bool in = active && c == c0;
+    f(in, c0, leader);
+    todo &= ~__ballot(in);
+  }
+}
+__device__ __forceinline__ void class_add(bool in, int leader, int64_t* row, int c0, int64_t v) {
+  const int64_t s = tnp::wave_sum(in ? v : (int64_t)0);
+  if (tnp::lane() == leader && s)
+    atomicAdd(reinterpret_cast<unsigned long long*>(row + c0), (unsigned long long)s);
+}
+
+// fp32 <-> a uint32 that orders the same way (for integer atomicMin / atomicMax)
+__device__ __forceinline__ uint32_t f32_ord(float f) {
+  const uint32_t b = __float_as_uint(f);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float ord_f32(uint32_t o) {
+  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
+}
+
+// one key per index position i, as k_poly_edges of polygons.hip:
+// (min << 32) | (max << 1) | (from > to), and the polygon that uses it
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_topo_edges(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n, int64_t V,
+             int64_t* __restrict__ ctr, uint64_t* __restrict__ keys, int32_t* __restrict__ pol) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  int64_t a, b;
+  bool b_ok;
+  uint64_t key = 0;
+  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok) && b_ok) {
+    const uint64_t lo = (uint64_t)(a < b ? a : b), hi = (uint64_t)(a < b ? b : a);
+    key = (lo << 32) | (hi << 1) | (a > b ? 1u : 0u);
+  }
+  keys[i] = key;
+  pol[i] = (int32_t)soup_polygon_of(off, P, i);
+}
+
+__global__ void __launch_bounds__(TNP_BLOCK) k_iota(int* __restrict__ a, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i < n) a[i] = (int)i;
+}
+
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_union_edges(const uint64_t* __restrict__ sk, const int32_t* __restrict__ sp, int64_t n, int* parent) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i < 1 || i >= n) return;
+  if ((sk[i] >> 1) == (sk[i - 1] >> 1)) uf_union(parent, sp[i], sp[i - 1]);
+}
+
+// connect = 1 (checked ids): the smallest polygon at each vertex, then every
+// polygon united with the owner of each of its vertices
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_vertex_owner(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n,
+               unsigned* __restrict__ vown) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  atomicMin(vown + idx[i], (unsigned)soup_polygon_of(off, P, i));
+}
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_union_vertices(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n,
+                 const unsigned* __restrict__ vown, int* parent) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  uf_union(parent, (int)soup_polygon_of(off, P, i), (int)vown[idx[i]]);
+}
+
+// sorted keys: position i is an edge used exactly once
+__device__ __forceinline__ bool lone_run(const uint64_t* __restrict__ sk, int64_t n, int64_t i) {
+  const uint64_t x = sk[i] >> 1;
+  return (i == 0 || (sk[i - 1] >> 1) != x) && (i + 1 == n || (sk[i + 1] >> 1) != x);
+}
+
+// one union per boundary edge; bdeg[v]: boundary edges at v; their number -> ctr[TC_B]
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_boundary_union(const uint64_t* __restrict__ sk, int64_t n, int* vparent, int* __restrict__ bdeg,
+                 int64_t* __restrict__ ctr) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  const bool lone = i < n && lone_run(sk, n, i);
+  if (lone) {
+    const int a = (int)(sk[i] >> 32), b = (int)((sk[i] >> 1) & 0x7fffffffu);
+    uf_union(vparent, a, b);
+    atomicAdd(bdeg + a, 1);
+    atomicAdd(bdeg + b, 1);
+  }
+  const uint64_t m = __ballot(lone);
+  if (tnp::lane() == 0 && m)
+    atomicAdd(reinterpret_cast<unsigned long long*>(ctr + TC_B), (unsigned long long)__popcll(m));
+}
+
+// flag[i] = i is a root (and, with deg, carries at least one boundary edge)
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_flag_roots(const int* __restrict__ parent, const int* __restrict__ deg, int64_t n, int32_t* __restrict__ flag) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i < n) flag[i] = parent[i] == (int)i && (!deg || deg[i] > 0);
+}
+
+// the flatten pass: every polygon takes the rank of its root
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_labels(int* parent, const int64_t* __restrict__ rank, int64_t P, int32_t* __restrict__ label,
+         int64_t* __restrict__ cnt, int64_t C) {
+  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (p >= P) return;
+  const int r = uf_find(parent, (int)p);
+  const int32_t c = (int32_t)rank[r];
+  label[p] = c;
+  if (r == (int)p) cnt[CK_FIRST * C + c] = p;
+}
+
+// per polygon: its degree and its vertices' box into its component; its fp32
+// area (the report's) and the double fan determinant, by polygon id
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_comp_polys(const float* __restrict__ xyz, const int64_t* __restrict__ off, const int64_t* __restrict__ idx,
+             int64_t P, const int32_t* __restrict__ label, int64_t* __restrict__ cnt, uint32_t* __restrict__ box,
+             int64_t C, double* __restrict__ parea, double* __restrict__ pdet) {
+  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  const bool active = p < P;
+  int c = 0;
+  int64_t deg = 0;
+  uint32_t lo[3] = {~0u, ~0u, ~0u}, hi[3] = {0u, 0u, 0u};
+  if (active) {
+    c = label[p];
+    const int64_t a = off[p], b = off[p + 1];
+    deg = b - a;
+    for (int64_t i = a; i < b; ++i) {
+      const float* q = xyz + 3 * idx[i];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        const uint32_t o = f32_ord(q[k]);
+        lo[k] = o < lo[k] ? o : lo[k];
+        hi[k] = o > hi[k] ? o : hi[k];
+      }
+    }
+    float cm[3], N[3];
+    parea[p] = (double)newell_area(xyz, idx, a, b, cm, N);
+    const float* q0 = xyz + 3 * idx[a];
+    const double p0[3] = {(double)q0[0], (double)q0[1], (double)q0[2]};
+    double det = 0.0;
+    for (int64_t i = a + 1; i + 1 < b; ++i) {
+      const float* q1 = xyz + 3 * idx[i];
+      const float* q2 = xyz + 3 * idx[i + 1];
+      const double u[3] = {(double)q1[0], (double)q1[1], (double)q1[2]};
+      const double v[3] = {(double)q2[0], (double)q2[1], (double)q2[2]};
+      det += p0[0] * (u[1] * v[2] - u[2] * v[1]) + p0[1] * (u[2] * v[0] - u[0] * v[2]) +
+             p0[2] * (u[0] * v[1] - u[1] * v[0]);
+    }
+    pdet[p] = det;
+  }
+  wave_classes(active, c, [&](bool in, int c0, int leader) {
+    class_add(in, leader, cnt + CK_NIDX * C, c0, deg);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      uint32_t l = in ? lo[k] : ~0u, h = in ? hi[k] : 0u;
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) {
+        const uint32_t l2 = __shfl_xor(l, o, 64), h2 = __shfl_xor(h, o, 64);
+        l = l2 < l ? l2 : l;
+        h = h2 > h ? h2 : h;
+      }
+      if (tnp::lane() == leader) {
+        atomicMin(box + (int64_t)k * C + c0, l);
+        atomicMax(box + (int64_t)(3 + k) * C + c0, h);
+      }
+    }
+  });
+}
+
+// sorted (key, polygon): the first use of every undirected edge classifies it
+// as k_edge_runs of polygons.hip does, into the component of its polygon
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_edge_stats(const uint64_t* __restrict__ k, const int32_t* __restrict__ sp, int64_t n,
+             const int32_t* __restrict__ label, int64_t* __restrict__ cnt, int64_t C) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  bool head = false, two = false, more = false, miso = false;
+  int c = 0;
+  if (i < n) {
+    const uint64_t x = k[i];
+    head = i == 0 || (k[i - 1] >> 1) != (x >> 1);
+    if (head) {
+      two = i + 1 < n && (k[i + 1] >> 1) == (x >> 1);
+      more = two && i + 2 < n && (k[i + 2] >> 1) == (x >> 1);
+      miso = two && !more && ((k[i + 1] ^ x) & 1) == 0;
+      c = label[sp[i]];
+    }
+  }
+  wave_classes(head, c, [&](bool in, int c0, int leader) {
+    class_add(in, leader, cnt + CK_EDGES * C, c0, 1);
+    class_add(in, leader, cnt + CK_BOUND * C, c0, !two);
+    class_add(in, leader, cnt + CK_MANI * C, c0, two && !more);
+    class_add(in, leader, cnt + CK_NONM * C, c0, more);
+    class_add(in, leader, cnt + CK_MISO * C, c0, miso);
+  });
+}
+
+// (label << vbits) | vertex of every index position
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_vertex_keys(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n,
+              const int32_t* __restrict__ label, int vbits, uint64_t* __restrict__ keys) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i < n) keys[i] = ((uint64_t)label[soup_polygon_of(off, P, i)] << vbits) | (uint64_t)idx[i];
+}
+
+// sorted keys: every distinct key adds one to the counter of its class key >> shift
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_key_runs(const uint64_t* __restrict__ k, int64_t n, int shift, int64_t* __restrict__ row) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  const bool head = i < n && (i == 0 || k[i - 1] != k[i]);
+  const int c = head ? (int)(k[i] >> shift) : 0;
+  wave_classes(head, c, [&](bool in, int c0, int leader) { class_add(in, leader, row, c0, 1); });
+}
+
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_poly_keys(const int32_t* __restrict__ label, int64_t P, int pbits, uint64_t* __restrict__ keys) {
+  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (p < P) keys[p] = ((uint64_t)label[p] << pbits) | (uint64_t)p;
+}
+
+// sorted keys (class << shift | member), every class present: start[c] = the
+// first position of class c, start[nseg] = n
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_seg_starts(const uint64_t* __restrict__ k, int64_t n, int shift, int64_t nseg, int64_t* __restrict__ start) {
+  const int64_t j = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (j == 0) start[nseg] = n;
+  if (j >= n) return;
+  const uint64_t c = k[j] >> shift;
+  if (j == 0 || (k[j - 1] >> shift) != c) start[c] = j;
+}
+
+// the values the segmented sums add, by the member bits of a key
+struct PolyVals {  // a polygon's area and fan determinant
+  const double* area;
+  const double* det;
+  __device__ __forceinline__ void operator()(uint64_t p, double* out) const {
+    out[0] = area[p];
+    out[1] = det[p];
+  }
+};
+struct EdgeLength {  // the length of the edge at sorted position i
+  const uint64_t* sk;
+  const float* xyz;
+  __device__ __forceinline__ void operator()(uint64_t i, double* out) const {
+    const float* a = xyz + 3 * (sk[i] >> 32);
+    const float* b = xyz + 3 * ((sk[i] >> 1) & 0x7fffffffu);
+    const double dx = (double)b[0] - (double)a[0], dy = (double)b[1] - (double)a[1], dz = (double)b[2] - (double)a[2];
+    out[0] = sqrt(dx * dx + dy * dy + dz * dz);
+  }
+};
+
+// Segmented double sums, first level: the sorted positions in blocks of SEG.
+// A piece is a maximal run of one class inside a block; its sum is stored at
+// the position of its first member.  A block of one class and SEG members is
+// summed by the fixed xor tree, any other piece left to right by its first
+// thread: the shape depends on the keys alone.
+template <int NV, class F>
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_seg_pieces(const uint64_t* __restrict__ k, int64_t n, int shift, F vals, double* __restrict__ ps) {
+  __shared__ uint64_t lc[SEG];
+  __shared__ double lv[NV][SEG];
+  __shared__ double lw[NV][TNP_WAVES];
+  const int t = threadIdx.x;
+  const int64_t j0 = (int64_t)blockIdx.x * SEG, j = j0 + t;
+  const bool active = j < n;
+  double v[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = 0.0;
+  uint64_t c = ~0ull;
+  if (active) {
+    c = k[j] >> shift;
+    vals(k[j] & ((1ull << shift) - 1ull), v);
+  }
+  lc[t] = c;
+#pragma unroll
+  for (int q = 0; q < NV; ++q) lv[q][t] = v[q];
+  __syncthreads();
+  const bool whole = __syncthreads_and(active && c == lc[0]);
+  if (whole) {
+#pragma unroll
+    for (int q = 0; q < NV; ++q) {
+      double s = v[q];
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+      if (tnp::lane() == 0) lw[q][tnp::wave()] = s;
+    }
+    __syncthreads();
+    if (t == 0) {
+#pragma unroll
+      for (int q = 0; q < NV; ++q) {
+        double s = lw[q][0];
+#pragma unroll
+        for (int w = 1; w < TNP_WAVES; ++w) s += lw[q][w];
+        ps[(int64_t)q * n + j0] = s;
+      }
+    }
+    return;
+  }
+  if (active && (t == 0 || lc[t - 1] != c)) {
+    for (int e = t + 1; e < SEG && lc[e] == c; ++e) {
+#pragma unroll
+      for (int q = 0; q < NV; ++q) v[q] += lv[q][e];
+    }
+#pragma unroll
+    for (int q = 0; q < NV; ++q) ps[(int64_t)q * n + j] = v[q];
+  }
+}
+
+// second level, one wave per class: its pieces start at start[c] and at the
+// multiples of SEG inside (start[c], start[c + 1]); lane l adds pieces l,
+// l + 64, ... in order, then the xor tree.  out[q * nseg + c].
+template <int NV>
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_seg_final(const int64_t* __restrict__ start, int64_t nseg, int64_t n, const double* __restrict__ ps,
+            double* __restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * TNP_WAVES + tnp::wave();
+  if (c >= nseg) return;  // (a whole wave)
+  const int64_t s = start[c], e = start[c + 1];
+  const int64_t b0 = s / SEG, np = e > s ? (e - 1) / SEG - b0 + 1 : 0;
+  double v[NV];
+#pragma unroll
+  for (int q = 0; q < NV; ++q) v[q] = 0.0;
+  for (int64_t r = tnp::lane(); r < np; r += 64) {
+    const int64_t at = r == 0 ? s : (b0 + r) * SEG;
+#pragma unroll
+    for (int q = 0; q < NV; ++q) v[q] += ps[(int64_t)q * n + at];
+  }
+#pragma unroll
+  for (int q = 0; q < NV; ++q) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v[q] += __shfl_xor(v[q], o, 64);
+    if (tnp::lane() == 0) out[(int64_t)q * nseg + c] = v[q];
+  }
+}
+
+// per boundary vertex: its loop's vertex count, first vertex, simplicity
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_loop_verts(int* vparent, const int* __restrict__ bdeg, const int64_t* __restrict__ vrank, int64_t V,
+             int64_t* __restrict__ lcnt, int64_t L) {
+  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  const bool active = v < V && bdeg[v] > 0;
+  int l = 0;
+  if (active) {
+    const int r = uf_find(vparent, (int)v);
+    l = (int)vrank[r];
+    if (r == (int)v) lcnt[LK_FIRST * L + l] = v;
+    if (bdeg[v] != 2) lcnt[LK_NONSIMPLE * L + l] = 1;
+  }
+  wave_classes(active, l,
+               [&](bool in, int c0, int leader) { class_add(in, leader, lcnt + LK_NVERT * L, c0, 1); });
+}
+
+// (loop << nbits) | sorted position of every boundary edge, appended in any
+// order (the keys are distinct: the sort fixes the order); cur zeroed
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_loop_keys(const uint64_t* __restrict__ sk, int64_t n, int* vparent, const int64_t* __restrict__ vrank, int nbits,
+            uint64_t* __restrict__ keys, int64_t B, unsigned long long* __restrict__ cur) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  const bool lone = i < n && lone_run(sk, n, i);
+  const uint64_t m = __ballot(lone);
+  if (!m) return;
+  unsigned long long base = 0;
+  if (tnp::lane() == 0) base = atomicAdd(cur, (unsigned long long)__popcll(m));
+  base = __shfl(base, 0, 64);
+  if (lone) {
+    const int64_t at = (int64_t)base + tnp::mbcnt(m);
+    const uint64_t l = (uint64_t)vrank[uf_find(vparent, (int)(sk[i] >> 32))];
+    if (at < B) keys[at] = (l << nbits) | (uint64_t)i;
+  }
+}
+
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_comp_rows(int64_t C, const int64_t* __restrict__ cnt, const int64_t* __restrict__ start,
+            const uint32_t* __restrict__ box, const double* __restrict__ sums, tnp_component* __restrict__ out) {
+  const int64_t c = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (c >= C) return;
+  tnp_component r;
+  r.first_polygon = cnt[CK_FIRST * C + c];
+  r.n_polygons = start[c + 1] - start[c];
+  r.n_indices = cnt[CK_NIDX * C + c];
+  r.n_vertices = cnt[CK_NVERT * C + c];
+  r.n_edges = cnt[CK_EDGES * C + c];
+  r.e_boundary = cnt[CK_BOUND * C + c];
+  r.e_manifold = cnt[CK_MANI * C + c];
+  r.e_nonmanifold = cnt[CK_NONM * C + c];
+  r.e_misoriented = cnt[CK_MISO * C + c];
+  r.euler = r.n_vertices - r.n_edges + r.n_polygons;
+  r.area = sums[c];
+  r.volume = sums[C + c] / 6.0;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.lo[k] = ord_f32(box[(int64_t)k * C + c]);
+    r.hi[k] = ord_f32(box[(int64_t)(3 + k) * C + c]);
+  }
+  out[c] = r;
+}
+
+// lkeys: the sorted loop keys (a loop's first key is its smallest edge)
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_loop_rows(int64_t L, const int64_t* __restrict__ lcnt, const int64_t* __restrict__ lstart,
+            const uint64_t* __restrict__ lkeys, int nbits, const int32_t* __restrict__ sp,
+            const int32_t* __restrict__ label, const double* __restrict__ length,
+            tnp_boundary_loop* __restrict__ out) {
+  const int64_t l = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (l >= L) return;
+  tnp_boundary_loop r;
+  r.first_vertex = lcnt[LK_FIRST * L + l];
+  r.n_edges = lstart[l + 1] - lstart[l];
+  r.n_vertices = lcnt[LK_NVERT * L + l];
+  r.component = label[sp[lkeys[lstart[l]] & ((1ull << nbits) - 1ull)]];
+  r.length = length[l];
+  r.simple = lcnt[LK_NONSIMPLE * L + l] == 0;
+  r.reserved = 0;
+  out[l] = r;
+}
+
+// device scratch of one build, freed on the stream on every way out.  The
+// build reserves two blocks (before and after the class counts are known) and
+// carves its arrays out of them: a stream-ordered allocation that the pool
+// cannot serve from memory it still holds costs more than most of the kernels
+// here, and a build has some forty arrays.  An array that does not fit its
+// block gets an allocation of its own.
+struct Scratch {
+  hipStream_t s;
+  std::vector<void*> p;
+  char* cur = nullptr;
+  size_t left = 0;
+  explicit Scratch(hipStream_t st) : s(st) {}
+  ~Scratch() {
+    for (void* q : p) (void)hipFreeAsync(q, s);
+  }
+  static size_t pad(size_t bytes) { return ((bytes < 256 ? 256 : bytes) + 255) / 256 * 256; }
+  bool reserve(size_t bytes) {
+    cur = nullptr, left = 0;
+    void* q = alloc(bytes);
+    if (!q) return false;
+    cur = static_cast<char*>(q), left = pad(bytes);
+    return true;
+  }
+  void* get(size_t bytes) {
+    const size_t b = pad(bytes);
+    if (b <= left) {
+      void* q = cur;
+      cur += b, left -= b;
+      return q;
+    }
+    return alloc(bytes);
+  }
+  void* alloc(size_t bytes) {
+    void* q = nullptr;
+    if (hipMallocAsync(&q, bytes < 256 ? 256 : bytes, s) != hipSuccess) {
+      tnp_set_error("topology: hipMallocAsync of %zu bytes failed", bytes);
+      return nullptr;
+    }
+    p.push_back(q);
+    return q;
+  }
+  template <typename T>
+  T* arr(int64_t n) { return static_cast<T*>(get((size_t)(n > 0 ? n : 1) * sizeof(T))); }
+};
+
+// look-back state of one stand-alone scan launch (zeroed words, epoch 1)
+int scan_flags(Scratch& scr, const int32_t* flag, int64_t n, int64_t* rank, int64_t* total, hipStream_t s) {
+  const size_t words = (size_t)scan_tiles(n) + 1;
+  uint64_t* buf = scr.arr<uint64_t>((int64_t)words);
+  if (!buf) return -1;
+  TNP_CHECK(hipMemsetAsync(buf, 0, words * sizeof(uint64_t), s));
+  TnpLB lb{};
+  lb.ticket = reinterpret_cast<unsigned long long*>(buf);
+  lb.st = buf + 1;
+  lb.tbase = 0;
+  lb.epoch = 1;
+  lb.spin = -1;
+  lb.rc = nullptr;
+  return scan_i32_to_i64(flag, rank, n, total, lb, s);
+}
+
+int bits_for(int64_t n) {  // the smallest b >= 1 with 2^b >= n
+  int b = 1;
+  while (((int64_t)1 << b) < n) ++b;
+  return b;
+}
+
+void drop_tables(tnp_topology* t) {
+  if (t->label) (void)hipFree(t->label);
+  if (t->comps) (void)hipFree(t->comps);
+  if (t->loops) (void)hipFree(t->loops);
+  t->label = nullptr, t->comps = nullptr, t->loops = nullptr;
+  t->P = t->C = t->L = 0;
+}
+
+// the stage events of a timed build
+struct Stages {
+  bool on;
+  hipStream_t s;
+  std::vector<hipEvent_t> ev;
+  Stages(bool o, hipStream_t st) : on(o), s(st) {}
+  ~Stages() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  void mark() {
+    if (!on) return;
+    hipEvent_t e;
+    if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
+    (void)hipEventRecord(e, s);
+    ev.push_back(e);
+  }
+};
+
+#define TOPO_LAUNCH(kernel, count, ...)                                                              \
+  do {                                                                                                \
+    hipLaunchKernelGGL(kernel, dim3(tnp_grid(count)), dim3(TNP_BLOCK), 0, s, __VA_ARGS__);           \
+    TNP_CHECK(hipGetLastError());                                                                     \
+  } while (0)
+
+}  // namespace
+
+extern "C" int tnp_topology_create(tnp_topology** out, int device) {
+  if (!out) { tnp_set_error("topology: null handle pointer"); return -1; }
+  TNP_CHECK(hipSetDevice(device));
+  tnp_topology* t = new tnp_topology();
+  t->device = device;
+  *out = t;
+  return 0;
+}
+
+extern "C" void tnp_topology_destroy(tnp_topology* t) {
+  if (!t) return;
+  (void)hipSetDevice(t->device);
+  drop_tables(t);
+  delete t;
+}
+
+extern "C" int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n) {
+  if (!t) { tnp_set_error("topology: null handle"); return -1; }
+  t->timed = enable != 0;
+  if (ms)
+    for (int i = 0; i < n && i < TNP_TOPOLOGY_STAGES; ++i) ms[i] = i < t->n_ms ? t->ms[i] : 0.0;
+  return TNP_TOPOLOGY_STAGES;
+}
+
+extern "C" int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V, const int64_t* d_offsets,
+                                  const int64_t* d_indices, int64_t P, int connect, int64_t* n_components,
+                                  int64_t* n_loops, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!t) { tnp_set_error("topology: null handle"); return -1; }
+  if (n_components) *n_components = 0;
+  if (n_loops) *n_loops = 0;
+  TNP_CHECK(hipSetDevice(t->device));
+  TNP_CHECK(hipStreamSynchronize(s));  // (an earlier export may still read the tables)
+  drop_tables(t);
+  t->n_ms = 0;
+  if (connect != 0 && connect != 1) { tnp_set_error("topology: connect = %d (0: edge, 1: vertex)", connect); return -1; }
+  if (P < 0 || V < 0) { tnp_set_error("topology: P = %lld, V = %lld", (long long)P, (long long)V); return -1; }
+  if (V >= (int64_t)1 << 31) {
+    tnp_set_error("topology: V = %lld vertices; the edge keys hold ids below 2^31", (long long)V);
+    return -1;
+  }
+  if (P >= (int64_t)1 << 31) {
+    tnp_set_error("topology: P = %lld polygons; the labels hold ids below 2^31", (long long)P);
+    return -1;
+  }
+  if (P == 0) return 0;
+  if (!d_offsets || !d_indices || (V > 0 && !d_xyz)) { tnp_set_error("topology: null array"); return -1; }
+  Scratch scr(s);
+  Stages st(t->timed, s);
+  st.mark();
+
+  // ---- checks, edge keys ----
+  int64_t* ctr = scr.arr<int64_t>(TC_N);
+  if (!ctr) return -1;
+  int64_t h[TC_N];
+  for (int i = 0; i < TC_N; ++i) h[i] = 0;
+  h[TC_ERR] = (int64_t)SOUP_NONE;
+  TNP_CHECK(hipMemcpyAsync(ctr, h, sizeof(h), hipMemcpyHostToDevice, s));
+  TOPO_LAUNCH(k_soup_offsets, P, d_offsets, P, ctr, (int32_t*)nullptr);
+  TNP_CHECK(hipMemcpyAsync(h, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  TNP_CHECK(hipStreamSynchronize(s));
+  if ((unsigned long long)h[TC_ERR] != SOUP_NONE)
+    return soup_report_error("topology", (unsigned long long)h[TC_ERR], d_offsets, d_indices, V, s);
+  const int64_t n = h[TC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
+  const int vbits = bits_for(V), pbits = bits_for(P), nbits = bits_for(n);
+  const int key_bits = 32 + vbits;
+
+  const size_t pair_bytes = sort_pairs_u64_scratch_bytes(n, key_bits);
+  {  // everything up to the class counts
+    const size_t scan_words = (size_t)scan_tiles(P) + (size_t)scan_tiles(V) + 2;
+    const size_t need = 2 * Scratch::pad(n * sizeof(uint64_t)) + 2 * Scratch::pad(n * sizeof(int32_t)) +
+                        Scratch::pad(pair_bytes) + 2 * Scratch::pad(P * sizeof(int32_t)) +
+                        Scratch::pad(P * sizeof(int64_t)) + 4 * Scratch::pad(V * sizeof(int32_t)) +
+                        Scratch::pad(V * sizeof(int64_t)) + 2 * Scratch::pad(scan_words * sizeof(uint64_t));
+    if (!scr.reserve(need)) return -1;
+  }
+  uint64_t* ka = scr.arr<uint64_t>(n);
+  uint64_t* kb = scr.arr<uint64_t>(n);
+  int32_t* pa = scr.arr<int32_t>(n);
+  int32_t* pb = scr.arr<int32_t>(n);
+  void* pair_scr = scr.get(pair_bytes);
+  if (!ka || !kb || !pa || !pb || !pair_scr) return -1;
+  TOPO_LAUNCH(k_topo_edges, n, d_offsets, P, d_indices, n, V, ctr, ka, pa);
+  // the ids are read through from here on: the check's verdict first
+  TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  TNP_CHECK(hipStreamSynchronize(s));
+  if ((unsigned long long)h[TC_ERR] != SOUP_NONE)
+    return soup_report_error("topology", (unsigned long long)h[TC_ERR], d_offsets, d_indices, V, s);
+  st.mark();
+
+  uint64_t* sk = nullptr;
+  int32_t* sp = nullptr;
+  if (sort_pairs_u64(ka, kb, pa, pb, n, key_bits, pair_scr, pair_bytes, &sk, &sp, s)) return -1;
+  uint64_t* spare = sk == ka ? kb : ka;  // n words, free from here on
+  st.mark();
+
+  // ---- the polygons' classes ----
+  int* parent = scr.arr<int>(P);
+  int32_t* pflag = scr.arr<int32_t>(P);
+  int64_t* prank = scr.arr<int64_t>(P);
+  if (!parent || !pflag || !prank) return -1;
+  TOPO_LAUNCH(k_iota, P, parent, P);
+  if (connect == 0) {
+    TOPO_LAUNCH(k_union_edges, n, sk, sp, n, parent);
+  } else {
+    unsigned* vown = scr.arr<unsigned>(V);
+    if (!vown) return -1;
+    TNP_CHECK(hipMemsetAsync(vown, 0xFF, (size_t)V * sizeof(unsigned), s));
+    TOPO_LAUNCH(k_vertex_owner, n, d_offsets, P, d_indices, n, vown);
+    TOPO_LAUNCH(k_union_vertices, n, d_offsets, P, d_indices, n, vown, parent);
+  }
+  TOPO_LAUNCH(k_flag_roots, P, parent, (const int*)nullptr, P, pflag);
+  if (scan_flags(scr, pflag, P, prank, ctr + TC_C, s)) return -1;
+  st.mark();
+
+  // ---- the boundary graph's classes ----
+  int* vparent = scr.arr<int>(V);
+  int* bdeg = scr.arr<int>(V);
+  int32_t* vflag = scr.arr<int32_t>(V);
+  int64_t* vrank = scr.arr<int64_t>(V);
+  if (!vparent || !bdeg || !vflag || !vrank) return -1;
+  TOPO_LAUNCH(k_iota, V, vparent, V);
+  TNP_CHECK(hipMemsetAsync(bdeg, 0, (size_t)(V > 0 ? V : 1) * sizeof(int), s));
+  TOPO_LAUNCH(k_boundary_union, n, sk, n, vparent, bdeg, ctr);
+  TOPO_LAUNCH(k_flag_roots, V, vparent, bdeg, V, vflag);
+  if (scan_flags(scr, vflag, V, vrank, ctr + TC_L, s)) return -1;
+  TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
+  TNP_CHECK(hipStreamSynchronize(s));
+  st.mark();
+  const int64_t C = h[TC_C], L = h[TC_L], B = h[TC_B];
+  if (C < 1 || C > P || L < 0 || L > B) {
+    tnp_set_error("topology: %lld components of %lld polygons, %lld loops of %lld boundary edges",
+                  (long long)C, (long long)P, (long long)L, (long long)B);
+    return -1;
+  }
+  const int cbits = bits_for(C), lbits = bits_for(L);
+  if (lbits + nbits > 64) { tnp_set_error("topology: %lld loops over %lld indices do not fit a key", (long long)L, (long long)n); return -1; }
+
+  // ---- the tables ----
+  TNP_CHECK(hipMalloc(&t->label, (size_t)P * sizeof(int32_t)));
+  TNP_CHECK(hipMalloc(&t->comps, (size_t)C * sizeof(tnp_component)));
+  if (L > 0) TNP_CHECK(hipMalloc(&t->loops, (size_t)L * sizeof(tnp_boundary_loop)));
+  const size_t vsort_bytes = sort_scratch_bytes(n, vbits + cbits);
+  const size_t psort_bytes = sort_scratch_bytes(P, pbits + cbits);
+  const size_t lsort_bytes = L > 0 ? sort_scratch_bytes(B, lbits + nbits) : 0;
+  {  // everything after them
+    const size_t need = Scratch::pad(CK_N * C * sizeof(int64_t)) + Scratch::pad(6 * C * sizeof(uint32_t)) +
+                        Scratch::pad((C + 1) * sizeof(int64_t)) + Scratch::pad(2 * C * sizeof(double)) +
+                        2 * Scratch::pad(P * sizeof(double)) + Scratch::pad(2 * std::max(P, B) * sizeof(double)) +
+                        Scratch::pad(n * sizeof(uint64_t)) + Scratch::pad(vsort_bytes) +
+                        2 * Scratch::pad(P * sizeof(uint64_t)) + Scratch::pad(psort_bytes) +
+                        Scratch::pad(LK_N * L * sizeof(int64_t)) + Scratch::pad((L + 1) * sizeof(int64_t)) +
+                        Scratch::pad(L * sizeof(double)) + 2 * Scratch::pad(B * sizeof(uint64_t)) +
+                        Scratch::pad(lsort_bytes) + Scratch::pad(sizeof(unsigned long long));
+    if (!scr.reserve(need)) return -1;
+  }
+  int64_t* cnt = scr.arr<int64_t>(CK_N * C);
+  uint32_t* box = scr.arr<uint32_t>(6 * C);
+  int64_t* cstart = scr.arr<int64_t>(C + 1);
+  double* csum = scr.arr<double>(2 * C);
+  double* parea = scr.arr<double>(P);
+  double* pdet = scr.arr<double>(P);
+  double* pieces = scr.arr<double>(2 * std::max(P, B));
+  if (!cnt || !box || !cstart || !csum || !parea || !pdet || !pieces) return -1;
+  {
+    FillOp ops[3] = {{cnt, (uint64_t)(CK_N * C) * sizeof(int64_t), 0u},
+                     {box, (uint64_t)(3 * C) * sizeof(uint32_t), 0xFFu},
+                     {box + 3 * C, (uint64_t)(3 * C) * sizeof(uint32_t), 0u}};
+    if (launch_fill(ops, 3, s)) return -1;
+  }
+  st.mark();
+
+  // ---- labels, per-component counts ----
+  TOPO_LAUNCH(k_labels, P, parent, prank, P, t->label, cnt, C);
+  TOPO_LAUNCH(k_comp_polys, P, d_xyz, d_offsets, d_indices, P, t->label, cnt, box, C, parea, pdet);
+  TOPO_LAUNCH(k_edge_stats, n, sk, sp, n, t->label, cnt, C);
+  st.mark();
+
+  // ---- distinct (label, vertex) ----
+  {
+    const int bits = vbits + cbits;
+    const size_t bytes = vsort_bytes;
+    uint64_t* va = spare;
+    uint64_t* vb = scr.arr<uint64_t>(n);
+    void* sscr = scr.get(bytes);
+    if (!vb || !sscr) return -1;
+    TOPO_LAUNCH(k_vertex_keys, n, d_offsets, P, d_indices, n, t->label, vbits, va);
+    uint64_t* sv = nullptr;
+    if (sort_keys_u64(va, vb, n, bits, sscr, bytes, &sv, s)) return -1;
+    TOPO_LAUNCH(k_key_runs, n, sv, n, vbits, cnt + CK_NVERT * C);
+  }
+  st.mark();
+
+  // ---- the polygons in (label, p) order ----
+  uint64_t* spk = nullptr;
+  {
+    const int bits = pbits + cbits;
+    const size_t bytes = psort_bytes;
+    uint64_t* qa = scr.arr<uint64_t>(P);
+    uint64_t* qb = scr.arr<uint64_t>(P);
+    void* sscr = scr.get(bytes);
+    if (!qa || !qb || !sscr) return -1;
+    TOPO_LAUNCH(k_poly_keys, P, t->label, P, pbits, qa);
+    if (sort_keys_u64(qa, qb, P, bits, sscr, bytes, &spk, s)) return -1;
+    TOPO_LAUNCH(k_seg_starts, P, spk, P, pbits, C, cstart);
+  }
+  st.mark();
+
+  // ---- area, volume ----
+  hipLaunchKernelGGL((k_seg_pieces<2, PolyVals>), dim3(tnp_grid(P, SEG)), dim3(TNP_BLOCK), 0, s, spk, P, pbits,
+                     PolyVals{parea, pdet}, pieces);
+  hipLaunchKernelGGL(k_seg_final<2>, dim3(tnp_grid(C, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, cstart, C, P, pieces, csum);
+  TNP_CHECK(hipGetLastError());
+  TOPO_LAUNCH(k_comp_rows, C, C, cnt, cstart, box, csum, t->comps);
+  st.mark();
+
+  // ---- the loops ----
+  if (L > 0) {
+    const int bits = lbits + nbits;
+    const size_t bytes = lsort_bytes;
+    int64_t* lcnt = scr.arr<int64_t>(LK_N * L);
+    int64_t* lstart = scr.arr<int64_t>(L + 1);
+    double* llen = scr.arr<double>(L);
+    uint64_t* la = scr.arr<uint64_t>(B);
+    uint64_t* lb = scr.arr<uint64_t>(B);
+    void* sscr = scr.get(bytes);
+    unsigned long long* cur = scr.arr<unsigned long long>(1);
+    if (!lcnt || !lstart || !llen || !la || !lb || !sscr || !cur) return -1;
+    TNP_CHECK(hipMemsetAsync(lcnt, 0, (size_t)(LK_N * L) * sizeof(int64_t), s));
+    TNP_CHECK(hipMemsetAsync(cur, 0, sizeof(unsigned long long), s));
+    TOPO_LAUNCH(k_loop_verts, V, vparent, bdeg, vrank, V, lcnt, L);
+    TOPO_LAUNCH(k_loop_keys, n, sk, n, vparent, vrank, nbits, la, B, cur);
+    uint64_t* sl = nullptr;
+    if (sort_keys_u64(la, lb, B, bits, sscr, bytes, &sl, s)) return -1;
+    TOPO_LAUNCH(k_seg_starts, B, sl, B, nbits, L, lstart);
+    hipLaunchKernelGGL((k_seg_pieces<1, EdgeLength>), dim3(tnp_grid(B, SEG)), dim3(TNP_BLOCK), 0, s, sl, B, nbits,
+                       EdgeLength{sk, d_xyz}, pieces);
+    hipLaunchKernelGGL(k_seg_final<1>, dim3(tnp_grid(L, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, lstart, L, B, pieces, llen);
+    TNP_CHECK(hipGetLastError());
+    TOPO_LAUNCH(k_loop_rows, L, L, lcnt, lstart, sl, nbits, sp, t->label, llen, t->loops);
+  }
+  st.mark();
+  TNP_CHECK(hipStreamSynchronize(s));
+  t->P = P, t->C = C, t->L = L;
+  if (st.on && (int)st.ev.size() == TNP_TOPOLOGY_STAGES + 1) {
+    for (int i = 0; i < TNP_TOPOLOGY_STAGES; ++i) {
+      float ms = 0.f;
+      (void)hipEventElapsedTime(&ms, st.ev[i], st.ev[i + 1]);
+      t->ms[i] = (double)ms;
+    }
+    t->n_ms = TNP_TOPOLOGY_STAGES;
+  }
+  if (n_components) *n_components = C;
+  if (n_loops) *n_loops = L;
+  return 0;
+}
+
+extern "C" int tnp_topology_export(tnp_topology* t, int32_t* d_label, tnp_component* d_components,
+                                   tnp_boundary_loop* d_loops, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (!t) { tnp_set_error("topology: null handle"); return -1; }
+  TNP_CHECK(hipSetDevice(t->device));
+  if (d_label && t->P > 0)
+    TNP_CHECK(hipMemcpyAsync(d_label, t->label, (size_t)t->P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+  if (d_components && t->C > 0)
+    TNP_CHECK(hipMemcpyAsync(d_components, t->comps, (size_t)t->C * sizeof(tnp_component), hipMemcpyDeviceToDevice, s));
+  if (d_loops && t->L > 0)
+    TNP_CHECK(hipMemcpyAsync(d_loops, t->loops, (size_t)t->L * sizeof(tnp_boundary_loop), hipMemcpyDeviceToDevice, s));
+  return 0;
+}

@@ -120,6 +120,11 @@ SIGNATURES = {
     "tnp_engine_polygons": (C.c_int, [_VP, _VP, _P64, _P64]),
     "tnp_engine_polygons_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "tnp_polygon_report": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpPolygonStats), _VP, _VP, _VP]),
+    "tnp_topology_create": (C.c_int, [C.POINTER(_VP), C.c_int]),
+    "tnp_topology_destroy": (None, [_VP]),
+    "tnp_topology_build": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, C.c_int, _P64, _P64, _VP]),
+    "tnp_topology_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "tnp_debug_topology_stages": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.c_int]),
     "tnp_render_raster": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpRenderView), _I32, _VP, _VP, _VP, _VP,
                                     C.POINTER(TnpRenderStats), _VP]),
     "tnp_render_shade": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I64, _F, _F, _VP, C.POINTER(C.c_uint8), _I32, _VP,

@@ -29,7 +29,14 @@ model and mesh file names then carry a `_l{layers}h{hidden}` suffix);
 --polygons also writes meshes/{d}/our_poly_mesh_{m}_{seed}.ply, the same
 surface as the convex polygons the triangles are fans of, and prints
 "Ours (polygons): P faces, mean degree D, edges E (boundary B, non-manifold
-N, misoriented M), euler X, max planarity dev Y" (tnp_polygon_report).
+N, misoriented M), euler X, max planarity dev Y" (tnp_polygon_report);
+--components (implies --polygons) then prints "Ours (components): C pieces
+(edge-connected), L boundary loops (S simple), longest loop N edges / length
+X", one line for each of the ten largest components by area (polygons, area,
+share of the total, boundary edges, Euler number, and the enclosed volume of a
+closed, consistently oriented one) and a count of the rest (tnp_topology_*);
+--keep-largest N (implies --components) also writes
+our_poly_mesh_{m}_{seed}_largest{N}.ply, the N largest components by area.
 """
 from __future__ import annotations
 
@@ -110,9 +117,18 @@ def parse_args(argv=None):
     p.add_argument("--out", default="meshes", help="mesh output directory")
     p.add_argument("--polygons", default=False, action="store_true",
                    help="also write the surface as convex polygons (our_poly_mesh_*.ply) and report its edges")
+    p.add_argument("--components", default=False, action="store_true",
+                   help="report the polygon surface's connected components and boundary loops (implies --polygons)")
+    p.add_argument("--keep-largest", default=0, type=int, metavar="N",
+                   help="also write the N largest components by area as our_poly_mesh_*_largestN.ply "
+                        "(implies --components)")
     p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
     p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
     args = p.parse_args(argv)
+    if args.keep_largest < 0:
+        p.error("--keep-largest: N >= 0")
+    args.components = args.components or args.keep_largest > 0
+    args.polygons = args.polygons or args.components
     try:
         check_shape(args.layers, args.hidden)
     except ValueError as e:
@@ -227,6 +243,36 @@ def export_polygons(pmesh: PolygonMesh, verts, path: str):
           f"euler {r['euler']}, max planarity dev {r['max_dev']:.3g}")
 
 
+def export_components(pmesh: PolygonMesh, verts, path: str, keep_largest: int = 0):
+    """--components: which pieces the polygon surface (over our_mesh's scaled
+    vertices `verts`) falls into and where its holes are; --keep-largest N
+    writes the N largest pieces by area next to `path`, the polygon file
+    (..._largestN.ply).  Returns the topology."""
+    from tropical.utils.topology import keep_components, largest_components, polygon_topology
+    pm = PolygonMesh(verts, pmesh.offsets, pmesh.indices, pmesh.normals)
+    topo = polygon_topology(pm.vertices, pm.offsets, pm.indices, connect="edge")
+    comps, loops = topo.components, topo.loops
+    longest = int(np.argmax(loops["n_edges"])) if len(loops) else -1  # (argmax: the lowest id among equals)
+    n_long, len_long = (int(loops["n_edges"][longest]), float(loops["length"][longest])) if len(loops) else (0, 0.0)
+    print(f"Ours (components): {len(comps)} pieces (edge-connected), {len(loops)} boundary loops "
+          f"({int(loops['simple'].sum())} simple), longest loop {n_long} edges / length {len_long:.6g}")
+    total = float(comps["area"].sum())
+    for c in largest_components(comps, 10, by="area"):
+        r = comps[c]
+        line = (f"  component {c}: {r['n_polygons']} polygons, area {r['area']:.6g} "
+                f"({100 * r['area'] / total if total > 0 else 0:.1f}%), boundary edges {r['e_boundary']}, "
+                f"euler {r['euler']}")
+        if r["e_boundary"] == 0 and r["e_nonmanifold"] == 0 and r["e_misoriented"] == 0:
+            line += f", volume {r['volume']:.6g}"
+        print(line)
+    if len(comps) > 10:
+        print(f"  and {len(comps) - 10} smaller components")
+    if keep_largest > 0:
+        kept = keep_components(pm, topo.labels, largest_components(comps, keep_largest, by="area"))
+        kept.export(f"{os.path.splitext(path)[0]}_largest{keep_largest}.ply")
+    return topo
+
+
 def train_sdf(net, args, path: str):
     """The training loop of train.py:153-231 (no checkpoint, or -c)."""
     from tropical.stanford.dataset import StanfordDataset
@@ -292,6 +338,8 @@ def main(argv=None):
     our_mesh.export(os.path.join(out_dir, f"our_mesh_{tag}.ply"))
     if args.polygons:
         export_polygons(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"))
+    if args.components:
+        export_components(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.keep_largest)
     if not args.eval:
         return 0
     evaluate(net, our_mesh, our_t, out_dir, tag)

@@ -10,7 +10,11 @@ transparent background and written as a PNG under {png_dir}/{d}/:
 
 Flags: -d dataset, -s seed, -m model size, --out DIR (the mesh directory), as
 `evaluate` has them; --size W H, --ssaa 1|2|4, --no-edges, --view ELEV AZIM
-(instead of the dataset's), --persp, --png-dir DIR (default `outputs`).
+(instead of the dataset's), --persp, --png-dir DIR (default `outputs`);
+--color component writes one more image of the polygon file,
+{m}_poly_components.png: the same raster, every polygon coloured by its
+edge-connected component's rank by area (tropical.utils.topology) through a
+qualitative table that repeats above 255.
 
 The reference draws with matplotlib's plot_trisurf and crops the figure; here
 csrc/render.hip rasterises the mesh and the camera is fitted to the box around
@@ -57,6 +61,8 @@ def parse_args(argv=None):
     p.add_argument("--view", nargs=2, type=float, default=None, metavar=("ELEV", "AZIM"),
                    help="view angles in degrees instead of the dataset's")
     p.add_argument("--persp", action="store_true", help="perspective projection")
+    p.add_argument("--color", default="normal", choices=["normal", "component"],
+                   help="component: one more image of the polygon file, coloured by connected component")
     return p.parse_args(argv)
 
 
@@ -93,6 +99,27 @@ def output_name(png_dir: str, dataset: str, model_size: str, suffix: str) -> str
     return os.path.join(png_dir, dataset, f"{model_size}_{suffix}.png")
 
 
+def component_lut() -> np.ndarray:
+    """A qualitative [256, 3] uint8 table: hues stepped by the golden angle,
+    three lightness / saturation bands, so neighbouring ranks differ."""
+    import colorsys
+    k = np.arange(256)
+    rgb = [colorsys.hls_to_rgb((0.61803398875 * i) % 1.0, (0.45, 0.6, 0.72)[i % 3], (0.85, 0.65, 0.75)[(i // 3) % 3])
+           for i in k]
+    return np.round(np.array(rgb) * 255).astype(np.uint8)
+
+
+def component_values(pm) -> torch.Tensor:
+    """Per polygon: its component's rank by area (largest 0), modulo 256, as float."""
+    from tropical.utils.topology import largest_components, polygon_topology
+    topo = polygon_topology(pm.vertices, pm.offsets, pm.indices, connect="edge")
+    order = largest_components(topo.components, topo.n_components, by="area")
+    rank = np.empty(topo.n_components, dtype=np.int64)
+    rank[order] = np.arange(topo.n_components)
+    rank_t = torch.from_numpy(rank % 256).to(topo.labels.device)
+    return rank_t[topo.labels.long()].float()
+
+
 def main(argv=None):
     args = parse_args(argv)
     print(args)
@@ -106,7 +133,7 @@ def main(argv=None):
         raise SystemExit("tropical.stanford.visualize needs a ROCm GPU (no CPU fallback)")
     from tropical.utils.image import write_png
     from tropical.utils.mesh import PolygonMesh, load_ply, load_polygon_ply
-    from tropical.utils.render import Camera, render
+    from tropical.utils.render import Camera, render, shade
     elev, azim, roll, vertical, swap_yz, proj, axis = VIEWS[args.dataset]
     if args.view is not None:
         elev, azim, roll = args.view[0], args.view[1], 0
@@ -135,6 +162,12 @@ def main(argv=None):
         print(f"{path} -> {out} ({len(pm)} faces)")
         if buf["stats"]["n_dropped"]:
             print(f"warning: {buf['stats']['n_dropped']} faces of {path} lie outside the view and were not drawn")
+        if args.color == "component" and suffix == "ours" and os.path.basename(path).startswith("our_poly_mesh"):
+            rgba = shade(buf["prim"], None if args.no_edges else buf["edge"], component_values(pm), 0.0, 255.0,
+                         component_lut(), ss=args.ssaa)
+            out = output_name(args.png_dir, args.dataset, args.model_size, "poly_components")
+            write_png(out, rgba)
+            print(f"{path} -> {out} (components)")
     return 0
 
 
