@@ -332,6 +332,73 @@ int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V, const int
 int tnp_topology_export(tnp_topology* t, int32_t* d_label, tnp_component* d_components,
                         tnp_boundary_loop* d_loops, void* stream);
 
+/* The boundary loops of a polygon soup as ordered cycles, and the caps that close them
+ * (csrc/holes.hip).  The result is again a polygon soup: the input polygons followed by the caps,
+ * the input vertices followed by the new ones.
+ *
+ * Input.  The polygon soup of tnp_polygon_report / tnp_topology_build, with the same checks, the same
+ * first-offender rule and the same message texts (prefix "holes"); V and P must be below 2^31.
+ * P = 0: no loops.  No coordinates are read by build.
+ *
+ * Boundary edges, loops, loop numbers, simple: exactly tnp_topology_build's.  A loop's number is its
+ * row number in the topology's loop table for the same soup.
+ *
+ * Direction.  A boundary edge is used once, by one polygon, which traverses it a -> b.  The cap
+ * traverses it b -> a: succ[b] = a, which makes the edge manifold and not misoriented.
+ *
+ * Status of a loop (int32), the rules tested in this order:
+ *  - TNP_HOLE_NONSIMPLE (1): simple = 0 (a pinch vertex: pairing the edges into cycles is a
+ *    geometric choice);
+ *  - TNP_HOLE_UNORIENTED (2): the loop is simple, but some vertex is the tail of two of its
+ *    reversed edges (and another is then the head of two): the surface flips orientation along it;
+ *  - TNP_HOLE_TOO_LONG (3): max_edges > 0 and n_edges > max_edges;
+ *  - TNP_HOLE_CAPPED (0): every other loop.
+ *  A simple loop has at least 3 edges: two boundary edges cannot share both ends.  Loops of status
+ *  1, 2 and 3 are counted and left open.
+ *
+ * Cycle.  The k-th capped loop, in loop order, is cycle k: c_0 is the loop's first_vertex (its
+ * smallest id), c_{i+1} = succ[c_i], the length m = n_edges.  Cycles are a function of the input alone.
+ *
+ * Caps, listed in cycle order.
+ *  - mode 0 (polygon): cap k is the polygon (c_0 ... c_{m-1}).  No vertex is added.
+ *  - mode 1 (star): a cycle with m = 3 is its own triangle.  A cycle with m >= 4 gets one new vertex
+ *    V + s, s being the cycle's rank among the cycles with m >= 4, and the m triangles
+ *    (c_i, c_{(i+1) mod m}, V + s), i = 0 ... m-1.  The new vertex is the mean of the cycle's fp32
+ *    coordinates: summed in double, divided by m once, rounded to fp32.  The sum's shape is fixed by
+ *    the input alone: the cycle positions in (cycle, i) order, cut into pieces at the multiples of
+ *    256 of that order and at the cycle boundaries; a piece that is a whole 256-block is summed by a
+ *    fixed tree, any other piece left to right; a cycle's pieces, in order, by 64 strided partial sums
+ *    and a fixed tree (the topology's shape).  No float atomics: the same bits on every call.
+ *
+ * build runs the checks, finds the loops, their status and the ordered cycles and keeps them in the
+ * handle (replacing those of an earlier build); it synchronises `stream`.  h_stats may be NULL.
+ * export copies status int32 [n_loops], cycle_loop int64 [n_capped] (the loop number of cycle k),
+ * cycle_offsets int64 [n_capped + 1] and cycle_vertices int64 [n_cycle_indices]; any may be NULL.
+ * caps writes the caps of the build held.  mode 0: n_capped polygons (d_cap_offsets, n_capped + 1)
+ * over n_cycle_indices ids; d_xyz and d_new_xyz are unused.  mode 1: n_triangles +
+ * (n_cycle_indices - 3 n_triangles) triangles (d_cap_offsets one more, d_cap_indices three each) and
+ * n_capped - n_triangles new vertices (d_new_xyz, fp32 x 3 each); d_xyz: the V x 3 input
+ * coordinates.  mode 1 synchronises `stream`. */
+#define TNP_HOLE_CAPPED 0
+#define TNP_HOLE_NONSIMPLE 1
+#define TNP_HOLE_UNORIENTED 2
+#define TNP_HOLE_TOO_LONG 3
+typedef struct tnp_hole_stats {
+  int64_t n_loops, n_capped, n_nonsimple, n_unoriented, n_too_long;
+  int64_t n_cycle_indices;   /* sum of the capped loops' n_edges */
+  int64_t n_triangles;       /* capped loops with 3 edges */
+  int64_t longest_capped;    /* edges; 0 when none */
+} tnp_hole_stats;
+typedef struct tnp_holes tnp_holes;
+int tnp_holes_create(tnp_holes** out, int device);
+void tnp_holes_destroy(tnp_holes* h);
+int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
+                    int64_t P, int64_t max_edges, tnp_hole_stats* h_stats, void* stream);
+int tnp_holes_export(tnp_holes* h, int32_t* d_status, int64_t* d_cycle_loop,
+                     int64_t* d_cycle_offsets, int64_t* d_cycle_vertices, void* stream);
+int tnp_holes_caps(tnp_holes* h, int mode, const float* d_xyz, int64_t* d_cap_offsets,
+                   int64_t* d_cap_indices, float* d_new_xyz, void* stream);
+
 /* 1: subpoly_(..., force=False) -- the curve-approximation branch
  * (subpoly.py:120-177, 201-207; geometry.py:24-138, 259-299;
  * subpoly_debug.py:121-165, 234-271): new vertices of non-axis-aligned split

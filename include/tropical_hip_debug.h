@@ -110,6 +110,12 @@ int tnp_debug_render_path(int mode);
 #define TNP_TOPOLOGY_STAGES 10
 int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n);
 
+/* Debug: stage times of tnp_holes_build (csrc/holes.hip), as tnp_debug_topology_stages: in the
+ * order check_edges, edge_sort, label_boundary, status, compact, rank, scatter.  A build that
+ * finds no loop records none.  Returns the number of stages (TNP_HOLES_STAGES), -1 on error. */
+#define TNP_HOLES_STAGES 7
+int tnp_debug_holes_stages(tnp_holes* h, int enable, double* ms, int n);
+
 #ifdef __cplusplus
 }
 #endif

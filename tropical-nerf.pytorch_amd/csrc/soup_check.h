@@ -1,9 +1,10 @@
 // The checks every entry point that takes a polygon soup (d_offsets int64
 // [P + 1], d_indices int64) makes on the device before anything is read
 // through an id -- tnp_polygon_report (polygons.hip), tnp_render_raster
-// (render.hip) and tnp_topology_build (topology.hip) share them, so all
-// refuse the same input and name the same first offender.  Included by those
-// three files only (anonymous namespace).
+// (render.hip), tnp_topology_build (topology.hip) and tnp_holes_build
+// (holes.hip) share them, so all refuse the same input and name the same
+// first offender.  Included by those four files only, the last two through
+// topo_common.h (anonymous namespace).
 //
 // ctr[SOUP_ERR]: the error word, (position << 3) | code under atomicMin, so
 // the smallest position wins; SOUP_NONE: no error.  ctr[SOUP_NIDX] = off[P].

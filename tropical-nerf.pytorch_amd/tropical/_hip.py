@@ -57,6 +57,14 @@ class TnpPolygonStats(C.Structure):
         return {k: (float if k in ("area", "max_dev") else int)(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TnpHoleStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_loops", "n_capped", "n_nonsimple", "n_unoriented", "n_too_long",
+                                         "n_cycle_indices", "n_triangles", "longest_capped")]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
 class TnpRenderView(C.Structure):
     _fields_ = [
         ("right", C.c_float * 3), ("up", C.c_float * 3), ("toward", C.c_float * 3), ("center", C.c_float * 3),
@@ -125,6 +133,12 @@ SIGNATURES = {
     "tnp_topology_build": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, C.c_int, _P64, _P64, _VP]),
     "tnp_topology_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP]),
     "tnp_debug_topology_stages": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.c_int]),
+    "tnp_holes_create": (C.c_int, [C.POINTER(_VP), C.c_int]),
+    "tnp_holes_destroy": (None, [_VP]),
+    "tnp_holes_build": (C.c_int, [_VP, _I64, _VP, _VP, _I64, _I64, C.POINTER(TnpHoleStats), _VP]),
+    "tnp_holes_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
+    "tnp_holes_caps": (C.c_int, [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP]),
+    "tnp_debug_holes_stages": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.c_int]),
     "tnp_render_raster": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpRenderView), _I32, _VP, _VP, _VP, _VP,
                                     C.POINTER(TnpRenderStats), _VP]),
     "tnp_render_shade": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I64, _F, _F, _VP, C.POINTER(C.c_uint8), _I32, _VP,

@@ -36,7 +36,13 @@ X", one line for each of the ten largest components by area (polygons, area,
 share of the total, boundary edges, Euler number, and the enclosed volume of a
 closed, consistently oriented one) and a count of the rest (tnp_topology_*);
 --keep-largest N (implies --components) also writes
-our_poly_mesh_{m}_{seed}_largest{N}.ply, the N largest components by area.
+our_poly_mesh_{m}_{seed}_largest{N}.ply, the N largest components by area;
+--fill-holes N (N >= 3, implies --components) caps every simple, consistently
+oriented boundary loop of at most N edges of that file (of the polygon file
+without --keep-largest) with one polygon, writes the result next to it as
+..._filled.ply and prints "Ours (holes): L loops, K capped (<= N edges), S
+non-simple, U unoriented, T longer; boundary edges B0 -> B1, closed components
+C0 -> C1" (tnp_holes_*).
 """
 from __future__ import annotations
 
@@ -122,12 +128,17 @@ def parse_args(argv=None):
     p.add_argument("--keep-largest", default=0, type=int, metavar="N",
                    help="also write the N largest components by area as our_poly_mesh_*_largestN.ply "
                         "(implies --components)")
+    p.add_argument("--fill-holes", default=0, type=int, metavar="N",
+                   help="also cap the simple boundary loops of at most N >= 3 edges of the last mesh written and "
+                        "write it as *_filled.ply (implies --components)")
     p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
     p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
     args = p.parse_args(argv)
     if args.keep_largest < 0:
         p.error("--keep-largest: N >= 0")
-    args.components = args.components or args.keep_largest > 0
+    if args.fill_holes < 0 or args.fill_holes in (1, 2):
+        p.error("--fill-holes: N >= 3 (a loop has at least 3 edges), or 0 for none")
+    args.components = args.components or args.keep_largest > 0 or args.fill_holes > 0
     args.polygons = args.polygons or args.components
     try:
         check_shape(args.layers, args.hidden)
@@ -273,6 +284,39 @@ def export_components(pmesh: PolygonMesh, verts, path: str, keep_largest: int = 
     return topo
 
 
+def _closed_components(comps) -> int:
+    return int(((comps["e_boundary"] == 0) & (comps["e_nonmanifold"] == 0) & (comps["e_misoriented"] == 0)).sum())
+
+
+def export_filled(pmesh: PolygonMesh, verts, path: str, max_edges: int, topo=None, keep_largest: int = 0):
+    """--fill-holes N: cap the simple boundary loops of at most N edges of the
+    mesh the run ends with -- the N largest pieces of --keep-largest (`topo`:
+    export_components' return), else the whole polygon surface -- with one
+    polygon each, write it next to that mesh's file (..._filled.ply) and print
+    what was closed.  Returns (filled mesh, stats)."""
+    from tropical.utils.topology import fill_holes, keep_components, largest_components, polygon_topology
+    pm = PolygonMesh(verts, pmesh.offsets, pmesh.indices, pmesh.normals)
+    base = os.path.splitext(path)[0]
+    if keep_largest > 0:
+        if topo is None:
+            topo = polygon_topology(pm.vertices, pm.offsets, pm.indices, connect="edge")
+        pm = keep_components(pm, topo.labels, largest_components(topo.components, keep_largest, by="area"))
+        base = f"{base}_largest{keep_largest}"
+        topo = None
+    if topo is None:
+        topo = polygon_topology(pm.vertices, pm.offsets, pm.indices, connect="edge")
+    filled, st = fill_holes(pm, max_edges=max_edges, mode="polygon")
+    filled.export(f"{base}_filled.ply")
+    b0 = polygon_report(pm.vertices, pm.offsets, pm.indices)["e_boundary"]
+    b1 = polygon_report(filled.vertices, filled.offsets, filled.indices)["e_boundary"]
+    c0 = _closed_components(topo.components)
+    c1 = _closed_components(polygon_topology(filled.vertices, filled.offsets, filled.indices, connect="edge").components)
+    print(f"Ours (holes): {st['n_loops']} loops, {st['n_capped']} capped (<= {max_edges} edges), "
+          f"{st['n_nonsimple']} non-simple, {st['n_unoriented']} unoriented, {st['n_too_long']} longer; "
+          f"boundary edges {b0} -> {b1}, closed components {c0} -> {c1}")
+    return filled, st
+
+
 def train_sdf(net, args, path: str):
     """The training loop of train.py:153-231 (no checkpoint, or -c)."""
     from tropical.stanford.dataset import StanfordDataset
@@ -339,7 +383,10 @@ def main(argv=None):
     if args.polygons:
         export_polygons(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"))
     if args.components:
-        export_components(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.keep_largest)
+        topo = export_components(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.keep_largest)
+        if args.fill_holes:
+            export_filled(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.fill_holes, topo,
+                          args.keep_largest)
     if not args.eval:
         return 0
     evaluate(net, our_mesh, our_t, out_dir, tag)
