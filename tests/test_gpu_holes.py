@@ -148,29 +148,6 @@ def test_max_edges_on_the_punched_grid(cuda, max_edges):
     assert st["longest_capped"] == {4: 4, 10: 10, 0: 96}[max_edges]
 
 
-def test_malformed_soups_raise_as_the_report_does(cuda):
-    from tropical.utils.mesh import polygon_report
-    from tropical.utils.topology import boundary_cycles
-    v, off, idx = soups()["cube"]
-    bad = [
-        (np.array([0, 4, 6, 12, 16, 20, 24]), idx, r"polygon 1 has 2 ids, fewer than 3"),
-        (off, np.where(np.arange(24) == 5, 99, idx), r"indices\[5\] = 99 is outside \[0, 8\)"),
-        (off, np.where(np.arange(24) == 9, idx[10], idx), r"indices\[9\] = 5 and the next id of its polygon are equal"),
-        (np.array([0, 4, 8, 6, 16, 20, 24]), idx, r"offsets decrease at polygon 2"),
-        (off, np.where(np.arange(24) % 7 == 3, 1 << 40, idx), r"indices\[3\] = 1099511627776 is outside"),
-    ]
-    for o, i, msg in bad:
-        with pytest.raises(RuntimeError, match=msg) as eh:
-            boundary_cycles(v, o, i)
-        with pytest.raises(RuntimeError) as er:
-            polygon_report(v, o, i)
-        assert str(eh.value).split("holes: ", 1)[1] == str(er.value).split("polygon_report: ", 2)[2]
-        # the next good call still works
-        assert boundary_cycles(*soups()["cylinder"]).stats["n_capped"] == 2
-    with pytest.raises(RuntimeError, match="max_edges"):
-        boundary_cycles(v, off, idx, max_edges=-1)
-
-
 def test_train_fill_holes_flag(cuda, tmp_path, capsys):
     """train --fill-holes 6 --keep-largest 1 on a fixture net's surface (no
     dataset): the printed line, the file, and every other output unchanged."""

@@ -130,29 +130,6 @@ def test_a_second_build_replaces_the_first(cuda):
         h.close()
 
 
-def test_malformed_soups_raise_as_the_report_does(cuda):
-    from tropical.utils.mesh import polygon_report
-    from tropical.utils.topology import polygon_topology
-    v, off, idx = soups()["cube"]
-    bad = [
-        (np.array([0, 4, 6, 12, 16, 20, 24]), idx, r"polygon 1 has 2 ids, fewer than 3"),
-        (off, np.where(np.arange(24) == 5, 99, idx), r"indices\[5\] = 99 is outside \[0, 8\)"),
-        (off, np.where(np.arange(24) == 9, idx[10], idx), r"indices\[9\] = 5 and the next id of its polygon are equal"),
-        (np.array([0, 4, 8, 6, 16, 20, 24]), idx, r"offsets decrease at polygon 2"),
-        (off, np.where(np.arange(24) % 7 == 3, 1 << 40, idx), r"indices\[3\] = 1099511627776 is outside"),
-    ]
-    for o, i, msg in bad:
-        with pytest.raises(RuntimeError, match=msg) as et:
-            polygon_topology(v, o, i)
-        with pytest.raises(RuntimeError) as er:
-            polygon_report(v, o, i)
-        assert str(et.value).split("topology: ", 1)[1] == str(er.value).split("polygon_report: ", 2)[2]
-    with pytest.raises(ValueError, match="connect"):
-        polygon_topology(v, off, idx, connect="face")
-    # and the bad input cost nothing
-    assert polygon_topology(v, off, idx).components["volume"].tolist() == [8.0]
-
-
 def test_keep_the_largest_component(cuda):
     from tropical.utils.mesh import PolygonMesh, polygon_report
     from tropical.utils.topology import keep_components, largest_components, polygon_topology

@@ -9,43 +9,12 @@ the stages are listed in include/tropical_hip_debug.h), wall times (median of
 5, stream-synchronised) of the build + export, of each cap mode, of
 polygon_topology, and the ratio of the build to the topology."""
 import json
-import os
-import statistics
-import sys
-import time
 
-sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tropical-nerf.pytorch_amd"),
-                os.path.join(os.getcwd(), "tests")]
-import torch  # noqa: E402
-
-from golden_io import load  # noqa: E402
-from helpers import product_net  # noqa: E402
-from tropical._engine import engine_for  # noqa: E402
+from soup_surface import synth64h_surface, wall  # (first: it sets the import path)
 from tropical.utils.topology import (boundary_cycles, cycle_caps, holes_handle, polygon_topology,  # noqa: E402
                                      topology_handle)
 
-dev = torch.device("cuda", 0)
-net = product_net(load("synth64h"), dev)
-eng = engine_for(net)
-eng.lattice()
-eng.run_steps([])
-eng.surface()
-verts, _, _ = eng.export(edges=False)
-eng.faces()
-off, idx, nrm = eng.polygons()
-
-
-def wall(fn, reps=5):
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize(dev)
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize(dev)
-        ts.append((time.perf_counter() - t) * 1e3)
-    return round(statistics.median(ts), 4)
-
-
+_, verts, off, idx = synth64h_surface()
 V = int(verts.shape[0])
 th, hh = topology_handle(), holes_handle()
 topo = polygon_topology(verts, off, idx, handle=th)  # (warm: the allocator's pools, the sorts' first launch)

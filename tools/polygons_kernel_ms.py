@@ -6,46 +6,15 @@ faces_* entries; faces_poly_emit is F6, faces_fan_emit F5 for both outputs),
 and wall times (median of 5, stream-synchronised) of polygons() alone on
 cached rows and of polygon_report() on the result."""
 import json
-import os
-import statistics
-import sys
-import time
 
-sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tropical-nerf.pytorch_amd"),
-                os.path.join(os.getcwd(), "tests")]
-import torch  # noqa: E402
-
-from golden_io import load  # noqa: E402
-from helpers import product_net  # noqa: E402
-from tropical._engine import engine_for  # noqa: E402
+from soup_surface import synth64h_surface, wall  # (first: it sets the import path)
 from tropical.utils.mesh import polygon_report  # noqa: E402
 
-dev = torch.device("cuda", 0)
-net = product_net(load("synth64h"), dev)
-eng = engine_for(net)
-eng.lattice()
-eng.run_steps([])
-eng.surface()
-verts, _, _ = eng.export(edges=False)
-eng.faces()
-eng.polygons()  # (grows the buffers)
+eng, verts, _, _ = synth64h_surface()  # (grows the buffers)
 eng.kernel_timer(True)
 tri, _ = eng.faces()
 off, idx, nrm = eng.polygons()
 kt = eng.kernel_timer(False)
-
-
-def wall(fn, reps=5):
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize(dev)
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize(dev)
-        ts.append((time.perf_counter() - t) * 1e3)
-    return round(statistics.median(ts), 4)
-
-
 rep = polygon_report(verts, off, idx)
 out = {"config": "synth64h surface", "V": int(verts.shape[0]), "n_tri": int(tri.shape[0]),
        "n_poly": int(off.numel() - 1), "n_idx": int(idx.numel()),

@@ -16,34 +16,18 @@ recorded as profiles/render_kernel_stats.csv (both surfaces, 6 raster and 6
 shade calls each).  --png DIR also writes the two figures."""
 import json
 import os
-import statistics
 import sys
-import time
 
-sys.path[:0] = [os.getcwd(), os.path.join(os.getcwd(), "tropical-nerf.pytorch_amd"),
-                os.path.join(os.getcwd(), "tests")]
+from soup_surface import dev, synth64h_surface, wall  # (first: it sets the import path)
 import torch  # noqa: E402
 
-from golden_io import load  # noqa: E402
 from helpers import product_net  # noqa: E402
-from tropical._engine import engine_for  # noqa: E402
+from golden_io import load  # noqa: E402
 from tropical.utils.image import write_png  # noqa: E402
 from tropical.utils.render import Camera, newell_normals, rasterize, render, shade  # noqa: E402
 from tropical.utils.colormap import lut  # noqa: E402
 
-dev = torch.device("cuda", 0)
 png_dir = sys.argv[sys.argv.index("--png") + 1] if "--png" in sys.argv else None
-
-
-def wall(fn, reps=5):
-    ts = []
-    for _ in range(reps):
-        torch.cuda.synchronize(dev)
-        t = time.perf_counter()
-        fn()
-        torch.cuda.synchronize(dev)
-        ts.append((time.perf_counter() - t) * 1e3)
-    return round(statistics.median(ts), 4)
 
 
 def measure(name, verts, off, idx, size, ssaa):
@@ -67,13 +51,7 @@ def measure(name, verts, off, idx, size, ssaa):
                   render(soup[:3], cam, size=size, ssaa=ssaa, value=value))
 
 
-net = product_net(load("synth64h"), dev)
-eng = engine_for(net)
-eng.lattice()
-eng.run_steps([])
-eng.surface()
-verts, _, _ = eng.export(edges=False)
-off, idx, _ = eng.polygons()
+_, verts, off, idx = synth64h_surface()
 measure("synth64h", verts, off, idx, (2048, 2048), 2)
 
 import tropical.subpoly as sp  # noqa: E402

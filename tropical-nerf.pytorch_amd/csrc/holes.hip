@@ -1,11 +1,13 @@
 // tnp_holes_*: the boundary loops of a polygon soup as ordered cycles, and the
 // caps that close them (include/tropical_hip.h has the definitions).  The
-// front half is the topology's (topo_common.h); the loops get the same numbers.
+// front half is the topology's (soup_host.h's front, topo_common.h's
+// boundary_classes), so the loops get the same numbers; tnp_holes_build is
+// its stages in order, one function each, with the state in a HolesBuild.
 //
-//   k_soup_offsets, k_topo_edges    the soup's checks, one directed-edge key
+//   k_soup_offsets, k_soup_edges    the soup's checks, one directed-edge key
 //                     per index (no polygon: the direction is the key's bit 0)
 //   sort_keys_u64     the keys on the bits the ids need
-//   k_boundary_union, k_flag_roots, scan   the loops and their numbers
+//   boundary_classes  the loops and their numbers
 //   k_cap_edges       per edge used once, a -> b in its polygon: succ[b] = a,
 //                     kept as pred[a] = b, which is what the ranking follows
 //                     (a plain store: a vertex of a loop that is capped is
@@ -251,71 +253,31 @@ void drop_cycles(tnp_holes* h) {
   h->st = tnp_hole_stats{};
 }
 
-}  // namespace
+// the state of one build, handed from stage to stage
+struct HolesBuild {
+  tnp_holes* h;
+  int64_t V;
+  const int64_t *off, *idx;
+  int64_t P, max_edges;
+  hipStream_t s;
+  Scratch scr;
+  Stages st;
+  int64_t* ctr = nullptr;
+  int64_t c[HC_N] = {};  // the counters as last read back
+  int64_t n = 0, L = 0, B = 0, K = 0, M = 0;
+  uint64_t* sk = nullptr;
+  int *vparent = nullptr, *bdeg = nullptr, *outd = nullptr, *pred = nullptr;
+  int32_t *vflag = nullptr, *vloop = nullptr, *capflag = nullptr;
+  int64_t *vrank = nullptr, *cpos = nullptr, *lfirst = nullptr, *ledges = nullptr, *crank = nullptr, *loff = nullptr,
+          *srank = nullptr;
+  tnp_hole_stats hs = {};
+  int edges(), loops(), status(), cycles();  // the stages, in order
+};
 
-extern "C" int tnp_holes_create(tnp_holes** out, int device) {
-  if (!out) { tnp_set_error("holes: null handle pointer"); return -1; }
-  TNP_CHECK(hipSetDevice(device));
-  tnp_holes* h = new tnp_holes();
-  h->device = device;
-  *out = h;
-  return 0;
-}
-
-extern "C" void tnp_holes_destroy(tnp_holes* h) {
-  if (!h) return;
-  (void)hipSetDevice(h->device);
-  drop_cycles(h);
-  delete h;
-}
-
-extern "C" int tnp_debug_holes_stages(tnp_holes* h, int enable, double* ms, int n) {
-  if (!h) { tnp_set_error("holes: null handle"); return -1; }
-  h->timed = enable != 0;
-  if (ms)
-    for (int i = 0; i < n && i < TNP_HOLES_STAGES; ++i) ms[i] = i < h->n_ms ? h->ms[i] : 0.0;
-  return TNP_HOLES_STAGES;
-}
-
-extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets, const int64_t* d_indices, int64_t P,
-                               int64_t max_edges, tnp_hole_stats* h_stats, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!h) { tnp_set_error("holes: null handle"); return -1; }
-  if (h_stats) *h_stats = tnp_hole_stats{};
-  TNP_CHECK(hipSetDevice(h->device));
-  TNP_CHECK(hipStreamSynchronize(s));  // (an earlier export may still read the cycles)
-  drop_cycles(h);
-  h->n_ms = 0;
-  if (P < 0 || V < 0) { tnp_set_error("holes: P = %lld, V = %lld", (long long)P, (long long)V); return -1; }
-  if (max_edges < 0) { tnp_set_error("holes: max_edges = %lld (0: no limit)", (long long)max_edges); return -1; }
-  if (V >= (int64_t)1 << 31) {
-    tnp_set_error("holes: V = %lld vertices; the edge keys hold ids below 2^31", (long long)V);
-    return -1;
-  }
-  if (P >= (int64_t)1 << 31) {
-    tnp_set_error("holes: P = %lld polygons; the soup's checks hold ids below 2^31", (long long)P);
-    return -1;
-  }
-  h->V = V;
-  if (P == 0) return 0;
-  if (!d_offsets || !d_indices) { tnp_set_error("holes: null array"); return -1; }
-  Scratch scr(s, "holes");
-  Stages st(h->timed, s);
-  st.mark();
-
-  // ---- checks, edge keys ----
-  int64_t* ctr = scr.arr<int64_t>(HC_N);
-  if (!ctr) return -1;
-  int64_t c[HC_N];
-  for (int i = 0; i < HC_N; ++i) c[i] = 0;
-  c[TC_ERR] = (int64_t)SOUP_NONE;
-  TNP_CHECK(hipMemcpyAsync(ctr, c, sizeof(c), hipMemcpyHostToDevice, s));
-  TOPO_LAUNCH(k_soup_offsets, P, d_offsets, P, ctr, (int32_t*)nullptr);
-  TNP_CHECK(hipMemcpyAsync(c, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)c[TC_ERR] != SOUP_NONE)
-    return soup_report_error("holes", (unsigned long long)c[TC_ERR], d_offsets, d_indices, V, s);
-  const int64_t n = c[TC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
+// stages check_edges, edge_sort
+int HolesBuild::edges() {
+  n = soup_offsets("holes", scr, off, idx, V, P, &ctr, HC_N, s);
+  if (n < 0) return -1;
   const int key_bits = 32 + bits_for(V);
   const size_t sort_bytes = sort_scratch_bytes(n, key_bits);
   {  // everything up to the loop count
@@ -328,54 +290,45 @@ extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets
   uint64_t* kb = scr.arr<uint64_t>(n);
   void* sort_scr = scr.get(sort_bytes);
   if (!ka || !kb || !sort_scr) return -1;
-  TOPO_LAUNCH(k_topo_edges, n, d_offsets, P, d_indices, n, V, ctr, ka, (int32_t*)nullptr);
-  TNP_CHECK(hipMemcpyAsync(c, ctr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)c[TC_ERR] != SOUP_NONE)
-    return soup_report_error("holes", (unsigned long long)c[TC_ERR], d_offsets, d_indices, V, s);
+  SOUP_LAUNCH((k_soup_edges<false, false>), n, off, P, idx, n, V, ctr, ka, (uint8_t*)nullptr, (int32_t*)nullptr);
+  if (soup_verdict("holes", off, idx, V, ctr, c, 1, s)) return -1;
   st.mark();
-
-  uint64_t* sk = nullptr;
   if (sort_keys_u64(ka, kb, n, key_bits, sort_scr, sort_bytes, &sk, s)) return -1;
   st.mark();
+  return 0;
+}
 
-  // ---- the boundary graph's classes (the topology's loop numbers) ----
-  int* vparent = scr.arr<int>(V);
-  int* bdeg = scr.arr<int>(V);
-  int* outd = scr.arr<int>(V);
-  int* pred = scr.arr<int>(V);
-  int32_t* vflag = scr.arr<int32_t>(V);
-  int32_t* vloop = scr.arr<int32_t>(V);
-  int64_t* vrank = scr.arr<int64_t>(V);
-  int64_t* cpos = scr.arr<int64_t>(V);
+// stage label_boundary: the boundary graph's classes (the topology's loop
+// numbers) -> L, B; the reversed boundary edges
+int HolesBuild::loops() {
+  vparent = scr.arr<int>(V);
+  bdeg = scr.arr<int>(V);
+  outd = scr.arr<int>(V);
+  pred = scr.arr<int>(V);
+  vflag = scr.arr<int32_t>(V);
+  vloop = scr.arr<int32_t>(V);
+  vrank = scr.arr<int64_t>(V);
+  cpos = scr.arr<int64_t>(V);
   if (!vparent || !bdeg || !outd || !pred || !vflag || !vloop || !vrank || !cpos) return -1;
-  TOPO_LAUNCH(k_iota, V, vparent, V);
-  {
-    const uint64_t vb = (uint64_t)(V > 0 ? V : 1) * sizeof(int);
-    FillOp ops[3] = {{bdeg, vb, 0u}, {outd, vb, 0u}, {vloop, vb, 0u}};  // (vloop: a valid loop for every vertex)
-    if (launch_fill(ops, 3, s)) return -1;
-  }
-  TOPO_LAUNCH(k_boundary_union, n, sk, n, vparent, bdeg, ctr);
-  TOPO_LAUNCH(k_flag_roots, V, vparent, bdeg, V, vflag);
-  if (scan_flags(scr, vflag, V, vrank, ctr + TC_L, s)) return -1;
-  TOPO_LAUNCH(k_cap_edges, n, sk, n, pred, outd);
+  const uint64_t vb = (uint64_t)(V > 0 ? V : 1) * sizeof(int);
+  FillOp ops[3] = {{bdeg, vb, 0u}, {outd, vb, 0u}, {vloop, vb, 0u}};  // (vloop: a valid loop for every vertex)
+  if (launch_fill(ops, 3, s)) return -1;
+  if (boundary_classes(scr, sk, n, V, vparent, bdeg, vflag, vrank, ctr, s)) return -1;
+  SOUP_LAUNCH(k_cap_edges, n, sk, n, pred, outd);
   TNP_CHECK(hipMemcpyAsync(c, ctr, (TC_B + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
   st.mark();
-  const int64_t L = c[TC_L], B = c[TC_B];
+  L = c[TC_L], B = c[TC_B];
   if (L < 0 || L > B || L > V) {
     tnp_set_error("holes: %lld loops of %lld boundary edges", (long long)L, (long long)B);
     return -1;
   }
-  tnp_hole_stats hs = {};
   hs.n_loops = L;
-  if (L == 0) {
-    if (h_stats) *h_stats = hs;
-    h->st = hs;
-    return 0;
-  }
+  return 0;
+}
 
-  // ---- status, cycle numbers and offsets ----
+// stage status (L > 0): every loop's status, the cycles' numbers and offsets -> K, M, the stats
+int HolesBuild::status() {
   TNP_CHECK(hipMalloc(&h->status, (size_t)L * sizeof(int32_t)));
   {
     const size_t need = 2 * Scratch::pad(L * sizeof(int64_t)) + 4 * Scratch::pad(L * sizeof(int32_t)) +
@@ -383,29 +336,28 @@ extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets
                         3 * Scratch::pad(((size_t)scan_tiles(L) + 1) * sizeof(uint64_t));
     if (!scr.reserve(need)) return -1;
   }
-  int64_t* lfirst = scr.arr<int64_t>(L);
-  int64_t* ledges = scr.arr<int64_t>(L);
+  lfirst = scr.arr<int64_t>(L);
+  ledges = scr.arr<int64_t>(L);
   int* lflags = scr.arr<int>(L);
-  int32_t* capflag = scr.arr<int32_t>(L);
+  capflag = scr.arr<int32_t>(L);
   int32_t* lenflag = scr.arr<int32_t>(L);
   int32_t* starflag = scr.arr<int32_t>(L);
-  int64_t* crank = scr.arr<int64_t>(L);
-  int64_t* loff = scr.arr<int64_t>(L);
-  int64_t* srank = scr.arr<int64_t>(L);
-  if (!lfirst || !ledges || !lflags || !capflag || !lenflag || !starflag || !crank || !loff || !srank) return -1;
-  {
-    FillOp ops[2] = {{ledges, (uint64_t)L * sizeof(int64_t), 0u}, {lflags, (uint64_t)L * sizeof(int), 0u}};
-    if (launch_fill(ops, 2, s)) return -1;
-  }
-  TOPO_LAUNCH(k_hole_verts, V, vparent, bdeg, outd, vrank, V, vloop, lfirst, ledges, lflags);
-  TOPO_LAUNCH(k_hole_status, L, L, ledges, lflags, max_edges, h->status, capflag, lenflag, starflag, ctr);
+  crank = scr.arr<int64_t>(L);
+  loff = scr.arr<int64_t>(L);
+  srank = scr.arr<int64_t>(L);
+  if (!lfirst || !ledges || !lflags || !capflag || !lenflag || !starflag || !crank || !loff || !srank)
+    return -1;
+  FillOp ops[2] = {{ledges, (uint64_t)L * sizeof(int64_t), 0u}, {lflags, (uint64_t)L * sizeof(int), 0u}};
+  if (launch_fill(ops, 2, s)) return -1;
+  SOUP_LAUNCH(k_hole_verts, V, vparent, bdeg, outd, vrank, V, vloop, lfirst, ledges, lflags);
+  SOUP_LAUNCH(k_hole_status, L, L, ledges, lflags, max_edges, h->status, capflag, lenflag, starflag, ctr);
   if (scan_flags(scr, capflag, L, crank, ctr + HC_CAPPED, s)) return -1;
   if (scan_flags(scr, lenflag, L, loff, ctr + HC_NIDX, s)) return -1;
   if (scan_flags(scr, starflag, L, srank, ctr + HC_NSTAR, s)) return -1;
   TNP_CHECK(hipMemcpyAsync(c, ctr, sizeof(c), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
   st.mark();
-  const int64_t K = c[HC_CAPPED], M = c[HC_NIDX];
+  K = c[HC_CAPPED], M = c[HC_NIDX];
   hs.n_capped = K, hs.n_nonsimple = c[HC_NONSIMPLE], hs.n_unoriented = c[HC_UNORIENTED], hs.n_too_long = c[HC_TOOLONG];
   hs.n_cycle_indices = M, hs.n_triangles = c[HC_NTRI], hs.longest_capped = c[HC_LONGEST];
   if (K < 0 || K > L || M < 3 * K || M > B || M > V || c[HC_NSTAR] != K - hs.n_triangles ||
@@ -414,15 +366,19 @@ extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets
                   (long long)M, (long long)B);
     return -1;
   }
+  return 0;
+}
 
-  // ---- the capped loops' vertices, ranked and scattered ----
+// stages compact, rank, scatter: the capped loops' vertices, ranked and scattered into the cycles
+int HolesBuild::cycles() {
   TNP_CHECK(hipMalloc(&h->cycle_offsets, (size_t)(K + 1) * sizeof(int64_t)));
   if (K > 0) {
     TNP_CHECK(hipMalloc(&h->cycle_loop, (size_t)K * sizeof(int64_t)));
     TNP_CHECK(hipMalloc(&h->cycle_star, (size_t)K * sizeof(int64_t)));
     TNP_CHECK(hipMalloc(&h->cycle_vertices, (size_t)M * sizeof(int64_t)));
   }
-  TOPO_LAUNCH(k_cycle_rows, L, L, capflag, crank, loff, srank, K, M, h->cycle_loop, h->cycle_offsets, h->cycle_star);
+  SOUP_LAUNCH(k_cycle_rows, L, L, capflag, crank, loff, srank, K, M, h->cycle_loop, h->cycle_offsets,
+              h->cycle_star);
   if (K > 0) {
     {
       const size_t need = Scratch::pad(M * sizeof(int32_t)) + 2 * Scratch::pad(M * sizeof(uint64_t)) +
@@ -433,47 +389,70 @@ extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets
     uint64_t* wa = scr.arr<uint64_t>(M);
     uint64_t* wb = scr.arr<uint64_t>(M);
     if (!cvert || !wa || !wb) return -1;
-    TOPO_LAUNCH(k_flag_cverts, V, V, bdeg, vloop, capflag, vflag);
+    SOUP_LAUNCH(k_flag_cverts, V, V, bdeg, vloop, capflag, vflag);
     if (scan_flags(scr, vflag, V, cpos, ctr + HC_NCV, s)) return -1;
     // (a position the ranking does not reach stays a valid self pointer)
     TNP_CHECK(hipMemsetAsync(wa, 0, (size_t)M * sizeof(uint64_t), s));
     TNP_CHECK(hipMemsetAsync(cvert, 0, (size_t)M * sizeof(int32_t), s));
-    TOPO_LAUNCH(k_rank_init, V, V, vflag, cpos, pred, vloop, lfirst, M, cvert, wa);
+    SOUP_LAUNCH(k_rank_init, V, V, vflag, cpos, pred, vloop, lfirst, M, cvert, wa);
     st.mark();
     int rounds = 0;
     while (((int64_t)1 << rounds) < hs.longest_capped) ++rounds;
     for (int r = 0; r < rounds; ++r) {
-      TOPO_LAUNCH(k_rank_round, M, wa, wb, M);
+      SOUP_LAUNCH(k_rank_round, M, wa, wb, M);
       uint64_t* t = wa;
       wa = wb, wb = t;
     }
     st.mark();
-    TOPO_LAUNCH(k_cycle_scatter, M, M, wa, cvert, vloop, loff, ledges, h->cycle_vertices);
+    SOUP_LAUNCH(k_cycle_scatter, M, M, wa, cvert, vloop, loff, ledges, h->cycle_vertices);
   } else {
     st.mark();
     st.mark();
   }
   st.mark();
-  TNP_CHECK(hipStreamSynchronize(s));
-  h->st = hs;
-  h->n_star = K - hs.n_triangles;
-  if (st.on && (int)st.ev.size() == TNP_HOLES_STAGES + 1) {
-    for (int i = 0; i < TNP_HOLES_STAGES; ++i) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, st.ev[i], st.ev[i + 1]);
-      h->ms[i] = (double)ms;
-    }
-    h->n_ms = TNP_HOLES_STAGES;
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int tnp_holes_create(tnp_holes** out, int device) { return handle_create("holes", out, device); }
+
+extern "C" void tnp_holes_destroy(tnp_holes* h) { handle_destroy(h, drop_cycles); }
+
+extern "C" int tnp_debug_holes_stages(tnp_holes* h, int enable, double* ms, int n) {
+  return handle_stages("holes", h, enable, ms, n);
+}
+
+extern "C" int tnp_holes_build(tnp_holes* h, int64_t V, const int64_t* d_offsets, const int64_t* d_indices, int64_t P,
+                               int64_t max_edges, tnp_hole_stats* h_stats, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (h_stats) *h_stats = tnp_hole_stats{};
+  if (handle_use("holes", h)) return -1;
+  TNP_CHECK(hipStreamSynchronize(s));  // (an earlier export may still read the cycles)
+  drop_cycles(h);
+  h->n_ms = 0;
+  if (max_edges < 0) { tnp_set_error("holes: max_edges = %lld (0: no limit)", (long long)max_edges); return -1; }
+  if (soup_args("holes", V, P, true, false, nullptr, d_offsets, d_indices)) return -1;
+  h->V = V;
+  if (P == 0) return 0;
+  HolesBuild b{h, V, d_offsets, d_indices, P, max_edges, s, Scratch(s, "holes"), Stages(h->timed, s)};
+  b.st.mark();
+  if (b.edges() || b.loops()) return -1;
+  if (b.L > 0) {
+    if (b.status() || b.cycles()) return -1;
+    TNP_CHECK(hipStreamSynchronize(s));
+    h->n_star = b.K - b.hs.n_triangles;
+    handle_keep_ms(h, b.st);
   }
-  if (h_stats) *h_stats = hs;
+  h->st = b.hs;
+  if (h_stats) *h_stats = b.hs;
   return 0;
 }
 
 extern "C" int tnp_holes_export(tnp_holes* h, int32_t* d_status, int64_t* d_cycle_loop, int64_t* d_cycle_offsets,
                                 int64_t* d_cycle_vertices, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (!h) { tnp_set_error("holes: null handle"); return -1; }
-  TNP_CHECK(hipSetDevice(h->device));
+  if (handle_use("holes", h)) return -1;
   const int64_t L = h->st.n_loops, K = h->st.n_capped, M = h->st.n_cycle_indices;
   if (d_status && L > 0)
     TNP_CHECK(hipMemcpyAsync(d_status, h->status, (size_t)L * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
@@ -494,9 +473,8 @@ extern "C" int tnp_holes_export(tnp_holes* h, int32_t* d_status, int64_t* d_cycl
 extern "C" int tnp_holes_caps(tnp_holes* h, int mode, const float* d_xyz, int64_t* d_cap_offsets,
                               int64_t* d_cap_indices, float* d_new_xyz, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (!h) { tnp_set_error("holes: null handle"); return -1; }
+  if (handle_use("holes", h)) return -1;
   if (mode != 0 && mode != 1) { tnp_set_error("holes: mode = %d (0: polygon, 1: star)", mode); return -1; }
-  TNP_CHECK(hipSetDevice(h->device));
   if (mode == 0) return tnp_holes_export(h, nullptr, nullptr, d_cap_offsets, d_cap_indices, stream);
   const int64_t K = h->st.n_capped, M = h->st.n_cycle_indices, nt = h->st.n_triangles;
   const int64_t T = nt + (M - 3 * nt);
@@ -518,7 +496,7 @@ extern "C" int tnp_holes_caps(tnp_holes* h, int mode, const float* d_xyz, int64_
   double* pieces = scr.arr<double>(3 * M);
   double* sums = scr.arr<double>(3 * K);
   if (!keys || !pieces || !sums) return -1;
-  TOPO_LAUNCH(k_star_caps, M, M, K, h->cycle_offsets, h->cycle_star, h->cycle_vertices, h->V, T, shift, d_cap_offsets,
+  SOUP_LAUNCH(k_star_caps, M, M, K, h->cycle_offsets, h->cycle_star, h->cycle_vertices, h->V, T, shift, d_cap_offsets,
               d_cap_indices, keys);
   if (h->n_star > 0) {
     hipLaunchKernelGGL((k_seg_pieces<3, CycleXYZ>), dim3(tnp_grid(M, SEG)), dim3(TNP_BLOCK), 0, s, keys, M, shift,
@@ -526,7 +504,7 @@ extern "C" int tnp_holes_caps(tnp_holes* h, int mode, const float* d_xyz, int64_
     hipLaunchKernelGGL(k_seg_final<3>, dim3(tnp_grid(K, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, h->cycle_offsets, K, M,
                        pieces, sums);
     TNP_CHECK(hipGetLastError());
-    TOPO_LAUNCH(k_star_centres, K, K, h->cycle_offsets, h->cycle_star, sums, h->n_star, d_new_xyz);
+    SOUP_LAUNCH(k_star_centres, K, K, h->cycle_offsets, h->cycle_star, sums, h->n_star, d_new_xyz);
   }
   TNP_CHECK(hipStreamSynchronize(s));  // (the scratch is freed on the way out)
   return 0;

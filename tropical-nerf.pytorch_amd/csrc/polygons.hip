@@ -3,9 +3,9 @@
 // scratch is allocated per call on the caller's stream and freed.
 //
 //   k_soup_offsets  per polygon: the offsets are checked, degrees written
-//   k_poly_edges    per index: ids checked, one directed-edge key and one
-//                   used-vertex flag written (stores only -- nothing is loaded
-//                   through an id here)
+//   k_soup_edges    per index: ids checked, one directed-edge key and one
+//                   used-vertex flag written (soup_check.h; the front around
+//                   both is soup_host.h's)
 //   sort_keys_u64   the keys, on the bits the ids need
 //   k_edge_runs     run lengths of equal undirected edges -> five counters
 //   k_poly_geom     per polygon: fp32 Newell area and planarity deviation;
@@ -20,7 +20,7 @@
 #include "faces.h"
 #include "kernels.h"
 #include "poly_geom.h"
-#include "soup_check.h"
+#include "soup_host.h"
 #include "step.h"
 
 namespace {
@@ -29,26 +29,6 @@ namespace {
 enum { PC_ERR, PC_NIDX, PC_MAXDEG, PC_VUSED, PC_EDGES, PC_BOUND, PC_MANI, PC_NONM, PC_MISO, PC_DEV, PC_AREA, PC_N };
 // (the error word, the offsets kernel and the id check are soup_check.h's: PC_ERR / PC_NIDX are its two words)
 static_assert(PC_ERR == SOUP_ERR && PC_NIDX == SOUP_NIDX, "counter layout");
-
-// one key per index position i: the edge from idx[i] to the next id of its
-// polygon (cyclic), (min << 32) | (max << 1) | (from > to)
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_poly_edges(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n, int64_t V,
-             int64_t* __restrict__ ctr, uint8_t* __restrict__ used, uint64_t* __restrict__ keys) {
-  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  int64_t a, b;
-  bool b_ok;
-  uint64_t key = 0;
-  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok)) {
-    used[a] = 1;
-    if (b_ok) {
-      const uint64_t lo = (uint64_t)(a < b ? a : b), hi = (uint64_t)(a < b ? b : a);
-      key = (lo << 32) | (hi << 1) | (a > b ? 1u : 0u);
-    }
-  }
-  keys[i] = key;
-}
 
 // sorted keys: a run of equal key >> 1 is one undirected edge used run-length
 // times.  The run's first key classifies it from the two keys after it (the
@@ -160,84 +140,45 @@ k_area_total(const double* __restrict__ partial, int64_t n, int64_t* __restrict_
   }
 }
 
-// device scratch of one call, freed on the stream on every way out
-struct Scratch {
-  hipStream_t s;
-  std::vector<void*> p;
-  explicit Scratch(hipStream_t st) : s(st) {}
-  ~Scratch() {
-    for (void* q : p) (void)hipFreeAsync(q, s);
-  }
-  void* get(size_t bytes) {
-    void* q = nullptr;
-    if (hipMallocAsync(&q, bytes < 256 ? 256 : bytes, s) != hipSuccess) {
-      tnp_set_error("polygon_report: hipMallocAsync of %zu bytes failed", bytes);
-      return nullptr;
-    }
-    p.push_back(q);
-    return q;
-  }
-};
-
 }  // namespace
 
 extern "C" int tnp_polygon_report(const float* d_xyz, int64_t V, const int64_t* d_offsets, const int64_t* d_indices,
                                   int64_t P, tnp_polygon_stats* h_out, float* d_area, float* d_dev, void* stream) {
+  const char* who = "polygon_report";
   hipStream_t s = (hipStream_t)stream;
   if (!h_out) { tnp_set_error("polygon_report: null stats"); return -1; }
   *h_out = tnp_polygon_stats{};
-  if (P < 0 || V < 0) { tnp_set_error("polygon_report: P = %lld, V = %lld", (long long)P, (long long)V); return -1; }
-  if (V >= (int64_t)1 << 31) {
-    tnp_set_error("polygon_report: V = %lld vertices; the edge keys hold ids below 2^31", (long long)V);
-    return -1;
-  }
+  if (soup_args(who, V, P, false, P > 0, d_xyz, d_offsets, d_indices)) return -1;
   if (P == 0) return 0;
-  if (!d_offsets || !d_indices || (V > 0 && !d_xyz)) { tnp_set_error("polygon_report: null array"); return -1; }
-  Scratch scr(s);
-  int64_t* ctr = static_cast<int64_t*>(scr.get(PC_N * sizeof(int64_t)));
-  int32_t* deg = static_cast<int32_t*>(scr.get(P * sizeof(int32_t)));
-  if (!ctr || !deg) return -1;
-  int64_t h[PC_N];
-  for (int i = 0; i < PC_N; ++i) h[i] = 0;
-  h[PC_ERR] = (int64_t)SOUP_NONE;
-  TNP_CHECK(hipMemcpyAsync(ctr, h, sizeof(h), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_soup_offsets, dim3(tnp_grid(P)), dim3(TNP_BLOCK), 0, s, d_offsets, P, ctr, deg);
-  TNP_CHECK(hipGetLastError());
-  TNP_CHECK(hipMemcpyAsync(h, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[PC_ERR] != SOUP_NONE)
-    return soup_report_error("polygon_report", (unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
-  const int64_t n = h[PC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
+  Scratch scr(s, who);
+  int64_t* ctr = nullptr;
+  int32_t* deg = scr.arr<int32_t>(P);
+  if (!deg) return -1;
+  const int64_t n = soup_offsets(who, scr, d_offsets, d_indices, V, P, &ctr, PC_N, s, deg);
+  if (n < 0) return -1;
 
-  int bits = 1;
-  while (((int64_t)1 << bits) < V) ++bits;
-  const int key_bits = 32 + bits;  // min in [32, 32 + bits), max << 1 | direction below
+  const int key_bits = 32 + bits_for(V);  // min in [32, 32 + bits), max << 1 | direction below
   const size_t sort_bytes = sort_scratch_bytes(n, key_bits);
   const int64_t nblk = tnp_grid(P);
-  uint64_t* ka = static_cast<uint64_t*>(scr.get(n * sizeof(uint64_t)));
-  uint64_t* kb = static_cast<uint64_t*>(scr.get(n * sizeof(uint64_t)));
+  uint64_t* ka = scr.arr<uint64_t>(n);
+  uint64_t* kb = scr.arr<uint64_t>(n);
   void* sort_scr = scr.get(sort_bytes);
-  uint8_t* used = static_cast<uint8_t*>(scr.get((size_t)(V > 16 ? V : 16)));
-  double* partial = static_cast<double*>(scr.get(nblk * sizeof(double)));
+  uint8_t* used = scr.arr<uint8_t>(V > 16 ? V : 16);
+  double* partial = scr.arr<double>(nblk);
   if (!ka || !kb || !sort_scr || !used || !partial) return -1;
   TNP_CHECK(hipMemsetAsync(used, 0, (size_t)(V > 16 ? V : 16), s));
-  hipLaunchKernelGGL(k_poly_edges, dim3(tnp_grid(n)), dim3(TNP_BLOCK), 0, s, d_offsets, P, d_indices, n, V, ctr,
-                     used, ka);
-  TNP_CHECK(hipGetLastError());
+  SOUP_LAUNCH((k_soup_edges<true, false>), n, d_offsets, P, d_indices, n, V, ctr, ka, used, (int32_t*)nullptr);
   uint64_t* sorted = nullptr;
   if (sort_keys_u64(ka, kb, n, key_bits, sort_scr, sort_bytes, &sorted, s)) return -1;
   hipLaunchKernelGGL(k_edge_runs, dim3(std::min<unsigned>(tnp_grid(n), 256u)), dim3(TNP_BLOCK), 0, s, sorted, n, ctr);
   TNP_CHECK(hipGetLastError());
   if (launch_count_flags(used, V, ctr, PC_VUSED, s)) return -1;
   if (launch_max_i32(deg, P, ctr + PC_MAXDEG, s)) return -1;
-  hipLaunchKernelGGL(k_poly_geom, dim3((unsigned)nblk), dim3(TNP_BLOCK), 0, s, d_xyz, d_offsets, d_indices, P, ctr,
-                     d_area, d_dev, partial);
+  SOUP_LAUNCH(k_poly_geom, P, d_xyz, d_offsets, d_indices, P, ctr, d_area, d_dev, partial);
   hipLaunchKernelGGL(k_area_total, dim3(1), dim3(TNP_BLOCK), 0, s, partial, nblk, ctr);
   TNP_CHECK(hipGetLastError());
-  TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[PC_ERR] != SOUP_NONE)
-    return soup_report_error("polygon_report", (unsigned long long)h[PC_ERR], d_offsets, d_indices, V, s);
+  int64_t h[PC_N];
+  if (soup_verdict(who, d_offsets, d_indices, V, ctr, h, PC_N, s)) return -1;
   h_out->n_polygons = P;
   h_out->n_indices = n;
   h_out->max_degree = h[PC_MAXDEG];

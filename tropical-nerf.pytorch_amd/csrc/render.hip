@@ -2,8 +2,8 @@
 // for polygon soups (include/tropical_hip.h has the contract).  The engine is
 // not involved: scratch is allocated per call on the caller's stream and freed.
 //
-//   k_soup_offsets per polygon: the offsets are checked (soup_check.h, shared
-//                  with tnp_polygon_report)
+//   k_soup_offsets per polygon: the offsets are checked (soup_check.h; the
+//                  front around the checks is soup_host.h's)
 //   k_rv_ids       per index: ids checked (nothing is loaded through an id)
 //   k_rv_project   per vertex: fp32 projection to 1/16-pixel ints + 20-bit depth
 //   k_rv_fan       per polygon: triangle -> polygon map, dropped / degenerate
@@ -23,7 +23,7 @@
 
 #include "../../include/tropical_hip_debug.h"
 #include "kernels.h"
-#include "soup_check.h"
+#include "soup_host.h"
 
 namespace {
 
@@ -368,38 +368,6 @@ k_rv_shade(const int32_t* __restrict__ prim, const uint8_t* __restrict__ edge, c
   reinterpret_cast<uchar4*>(rgba)[o] = out;
 }
 
-// device scratch of one call, freed on the stream on every way out
-struct RvScratch {
-  hipStream_t s;
-  std::vector<void*> p;
-  explicit RvScratch(hipStream_t st) : s(st) {}
-  ~RvScratch() {
-    for (void* q : p) (void)hipFreeAsync(q, s);
-  }
-  void* get(size_t bytes) {
-    void* q = nullptr;
-    if (hipMallocAsync(&q, bytes < 256 ? 256 : bytes, s) != hipSuccess) {
-      tnp_set_error("render: hipMallocAsync of %zu bytes failed", bytes);
-      return nullptr;
-    }
-    p.push_back(q);
-    return q;
-  }
-};
-
-// look-back state of one stand-alone scan launch: `buf` zeroed once, a fresh
-// epoch per launch (common.h TnpLB; ticket-free, so no ticket base)
-TnpLB rv_lb(uint64_t* buf, uint32_t epoch) {
-  TnpLB lb{};
-  lb.ticket = reinterpret_cast<unsigned long long*>(buf);
-  lb.st = buf + 1;
-  lb.tbase = 0;
-  lb.epoch = epoch;
-  lb.spin = -1;
-  lb.rc = nullptr;
-  return lb;
-}
-
 int rv_view_check(const tnp_render_view* v, ViewDev* out) {
   if (!v) { tnp_set_error("render: null view"); return -1; }
   if (v->width < 1 || v->width > RV_MAX_DIM) {
@@ -437,33 +405,26 @@ extern "C" int tnp_render_raster(const float* d_xyz, int64_t V, const int64_t* d
                                  int64_t P, const tnp_render_view* view, int32_t edge_half_width, int32_t* d_screen,
                                  int32_t* d_prim, int32_t* d_tri, uint8_t* d_edge, tnp_render_stats* h_stats,
                                  void* stream) {
+  const char* who = "render";
   hipStream_t s = (hipStream_t)stream;
   if (!h_stats) { tnp_set_error("render: null stats"); return -1; }
   *h_stats = tnp_render_stats{};
   ViewDev vw;
   if (rv_view_check(view, &vw)) return -1;
-  if (P < 0 || V < 0) { tnp_set_error("render: P = %lld, V = %lld", (long long)P, (long long)V); return -1; }
-  if (V >= (int64_t)1 << 31 || P >= (int64_t)1 << 31) {
-    tnp_set_error("render: V = %lld vertices, P = %lld polygons; ids are held below 2^31", (long long)V, (long long)P);
-    return -1;
-  }
   if (edge_half_width < 0 || edge_half_width > 256) {
     tnp_set_error("render: edge_half_width = %d is outside [0, 256]", (int)edge_half_width);
     return -1;
   }
-  if (!d_prim || (V > 0 && !d_xyz) || (P > 0 && (!d_offsets || !d_indices))) {
-    tnp_set_error("render: null array");
-    return -1;
-  }
+  if (soup_args(who, V, P, true, true, d_xyz, d_offsets, d_indices)) return -1;
+  if (!d_prim) { tnp_set_error("render: null array"); return -1; }
   const int W = view->width, H = view->height;
   const int64_t npix = (int64_t)W * H;
-  RvScratch scr(s);
+  Scratch scr(s, who);
   int32_t* screen = d_screen;
-  if (!screen && V > 0) screen = static_cast<int32_t*>(scr.get((size_t)V * 3 * sizeof(int32_t)));
+  if (!screen && V > 0) screen = scr.arr<int32_t>(V * 3);
   if (V > 0) {
     if (!screen) return -1;
-    hipLaunchKernelGGL(k_rv_project, dim3(tnp_grid(V)), dim3(TNP_BLOCK), 0, s, d_xyz, V, vw, screen);
-    TNP_CHECK(hipGetLastError());
+    SOUP_LAUNCH(k_rv_project, V, d_xyz, V, vw, screen);
   }
   if (P == 0) {
     const FillOp ops[3] = {{d_prim, (uint64_t)npix * 4, 0xFFu}, {d_tri, d_tri ? (uint64_t)npix * 4 : 0, 0xFFu},
@@ -473,60 +434,41 @@ extern "C" int tnp_render_raster(const float* d_xyz, int64_t V, const int64_t* d
     return 0;
   }
 
-  int64_t* ctr = static_cast<int64_t*>(scr.get(RC_N * sizeof(int64_t)));
-  if (!ctr) return -1;
-  int64_t h[RC_N];
-  for (int i = 0; i < RC_N; ++i) h[i] = 0;
-  h[RC_ERR] = (int64_t)SOUP_NONE;
-  TNP_CHECK(hipMemcpyAsync(ctr, h, sizeof(h), hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_soup_offsets, dim3(tnp_grid(P)), dim3(TNP_BLOCK), 0, s, d_offsets, P, ctr,
-                     static_cast<int32_t*>(nullptr));
-  TNP_CHECK(hipGetLastError());
-  TNP_CHECK(hipMemcpyAsync(h, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[RC_ERR] != SOUP_NONE)
-    return soup_report_error("render", (unsigned long long)h[RC_ERR], d_offsets, d_indices, V, s);
-  const int64_t n = h[RC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
+  int64_t* ctr = nullptr;
+  const int64_t n = soup_offsets(who, scr, d_offsets, d_indices, V, P, &ctr, RC_N, s);
+  if (n < 0) return -1;
   const int64_t nT = n - 2 * P;  // >= P
   if (nT >= (int64_t)1 << 31) {
     tnp_set_error("render: %lld fan triangles; triangle numbers are held below 2^31", (long long)nT);
     return -1;
   }
-  hipLaunchKernelGGL(k_rv_ids, dim3(tnp_grid(n)), dim3(TNP_BLOCK), 0, s, d_offsets, P, d_indices, n, V, ctr);
-  TNP_CHECK(hipGetLastError());
-  TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-
-  // (independent of the ids: queued behind the check, ahead of its readback)
+  SOUP_LAUNCH(k_rv_ids, n, d_offsets, P, d_indices, n, V, ctr);
+  // (independent of the ids: queued behind the check, ahead of its verdict)
   const int64_t lb_words = scan_tiles(nT) + 1;
-  uint64_t* lbuf = static_cast<uint64_t*>(scr.get((size_t)lb_words * sizeof(uint64_t)));
-  unsigned long long* vis = static_cast<unsigned long long*>(scr.get((size_t)npix * sizeof(unsigned long long)));
+  uint64_t* lbuf = scr.arr<uint64_t>(lb_words);
+  unsigned long long* vis = scr.arr<unsigned long long>(npix);
   if (!lbuf || !vis) return -1;
   TNP_CHECK(hipMemsetAsync(lbuf, 0, (size_t)lb_words * sizeof(uint64_t), s));
   const FillOp clear = {vis, (uint64_t)npix * sizeof(unsigned long long), 0xFFu};
   if (launch_fill(&clear, 1, s)) return -1;
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[RC_ERR] != SOUP_NONE)
-    return soup_report_error("render", (unsigned long long)h[RC_ERR], d_offsets, d_indices, V, s);
+  int64_t h[RC_N];
+  if (soup_verdict(who, d_offsets, d_indices, V, ctr, h, 1, s)) return -1;
 
   // every id is now known to lie in [0, V): from here on ids are followed
-  int32_t* tpoly = static_cast<int32_t*>(scr.get((size_t)nT * sizeof(int32_t)));
-  int32_t* islarge = static_cast<int32_t*>(scr.get((size_t)nT * sizeof(int32_t)));
-  int64_t* loff = static_cast<int64_t*>(scr.get((size_t)nT * sizeof(int64_t)));
-  int32_t* list = static_cast<int32_t*>(scr.get((size_t)nT * sizeof(int32_t)));
-  uint8_t* pflag = static_cast<uint8_t*>(scr.get((size_t)P));
+  int32_t* tpoly = scr.arr<int32_t>(nT);
+  int32_t* islarge = scr.arr<int32_t>(nT);
+  int64_t* loff = scr.arr<int64_t>(nT);
+  int32_t* list = scr.arr<int32_t>(nT);
+  uint8_t* pflag = scr.arr<uint8_t>(P);
   if (!tpoly || !islarge || !loff || !list || !pflag) return -1;
-  hipLaunchKernelGGL(k_rv_fan, dim3(tnp_grid(P)), dim3(TNP_BLOCK), 0, s, d_offsets, d_indices, P, screen, tpoly,
-                     pflag, ctr);
-  hipLaunchKernelGGL(k_rv_small, dim3(tnp_grid(nT)), dim3(TNP_BLOCK), 0, s, d_offsets, d_indices, nT, screen,
-                     tpoly, pflag, W, H, g_path_mode, vis, islarge);
-  TNP_CHECK(hipGetLastError());
-  if (scan_i32_to_i64(islarge, loff, nT, ctr + RC_LARGE, rv_lb(lbuf, 1), s)) return -1;
-  hipLaunchKernelGGL(k_rv_compact, dim3(tnp_grid(nT)), dim3(TNP_BLOCK), 0, s, islarge, loff, nT, list);
+  SOUP_LAUNCH(k_rv_fan, P, d_offsets, d_indices, P, screen, tpoly, pflag, ctr);
+  SOUP_LAUNCH(k_rv_small, nT, d_offsets, d_indices, nT, screen, tpoly, pflag, W, H, g_path_mode, vis, islarge);
+  if (scan_i32_to_i64(islarge, loff, nT, ctr + RC_LARGE, scan_lb(lbuf), s)) return -1;
+  SOUP_LAUNCH(k_rv_compact, nT, islarge, loff, nT, list);
   hipLaunchKernelGGL(k_rv_large, dim3(RV_LARGE_GRID), dim3(TNP_BLOCK), 0, s, d_offsets, d_indices, screen, tpoly, list,
                      ctr, W, H, vis);
-  hipLaunchKernelGGL(k_rv_resolve, dim3(tnp_grid(npix)), dim3(TNP_BLOCK), 0, s, vis, W, H, d_offsets, d_indices,
-                     screen, tpoly, (int)edge_half_width, d_prim, d_tri, d_edge, ctr);
-  TNP_CHECK(hipGetLastError());
+  SOUP_LAUNCH(k_rv_resolve, npix, vis, W, H, d_offsets, d_indices, screen, tpoly, (int)edge_half_width, d_prim, d_tri,
+              d_edge, ctr);
   TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
   h_stats->n_polygons = P;

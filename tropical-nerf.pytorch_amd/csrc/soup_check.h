@@ -1,10 +1,10 @@
 // The checks every entry point that takes a polygon soup (d_offsets int64
 // [P + 1], d_indices int64) makes on the device before anything is read
-// through an id -- tnp_polygon_report (polygons.hip), tnp_render_raster
-// (render.hip), tnp_topology_build (topology.hip) and tnp_holes_build
-// (holes.hip) share them, so all refuse the same input and name the same
-// first offender.  Included by those four files only, the last two through
-// topo_common.h (anonymous namespace).
+// through an id, and the edge keys three of them build in the same pass --
+// tnp_polygon_report (polygons.hip), tnp_render_raster (render.hip),
+// tnp_topology_build (topology.hip) and tnp_holes_build (holes.hip) share
+// them, so all refuse the same input and name the same first offender.  The
+// host side around these kernels is soup_host.h's.
 //
 // ctr[SOUP_ERR]: the error word, (position << 3) | code under atomicMin, so
 // the smallest position wins; SOUP_NONE: no error.  ctr[SOUP_NIDX] = off[P].
@@ -69,6 +69,31 @@ __device__ __forceinline__ bool soup_check_id(const int64_t* __restrict__ off, i
   }
   if (a == b) soup_fail(ctr, i, SE_EQUAL);
   return true;
+}
+
+// one key per index position i: the edge from idx[i] to the next id of its
+// polygon (cyclic), (min << 32) | (max << 1) | (from > to); 0 after a failed
+// check.  USED: used[a] = 1 for every valid id; POL: pol[i] = the polygon of
+// position i.  Stores only -- nothing is loaded through an id.
+template <bool USED, bool POL>
+__global__ void __launch_bounds__(TNP_BLOCK)
+k_soup_edges(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n, int64_t V,
+             int64_t* __restrict__ ctr, uint64_t* __restrict__ keys, uint8_t* __restrict__ used,
+             int32_t* __restrict__ pol) {
+  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
+  if (i >= n) return;
+  int64_t a, b;
+  bool b_ok;
+  uint64_t key = 0;
+  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok)) {
+    if (USED) used[a] = 1;
+    if (b_ok) {
+      const uint64_t lo = (uint64_t)(a < b ? a : b), hi = (uint64_t)(a < b ? b : a);
+      key = (lo << 32) | (hi << 1) | (a > b ? 1u : 0u);
+    }
+  }
+  keys[i] = key;
+  if (POL) pol[i] = (int32_t)soup_polygon_of(off, P, i);
 }
 
 // the failed check of error word w as tnp_last_error(), prefixed `who`; the

@@ -1,13 +1,11 @@
-// What tnp_topology_build (topology.hip) and tnp_holes_build (holes.hip) share:
-// the lock-free union-find, the per-class wave reductions, the front half of
-// both builds (edge keys with the soup's checks, the boundary graph's union,
-// the root flags and their scan), the segmented double sums and the scratch
-// of one build.  Included by those two files only (anonymous namespace).
+// What tnp_topology_build (topology.hip) and tnp_holes_build (holes.hip) share
+// beyond soup_host.h: the lock-free union-find, the per-class wave reductions,
+// the boundary graph's classes (one union per edge used once, the root flags
+// and their scan) and the segmented double sums.  Included by those two files
+// only (anonymous namespace).
 #pragma once
-#include <vector>
-
 #include "kernels.h"
-#include "soup_check.h"
+#include "soup_host.h"
 #include "step.h"
 
 namespace {
@@ -79,25 +77,6 @@ __device__ __forceinline__ void class_add(bool in, int leader, int64_t* row, int
   const int64_t s = tnp::wave_sum(in ? v : (int64_t)0);
   if (tnp::lane() == leader && s)
     atomicAdd(reinterpret_cast<unsigned long long*>(row + c0), (unsigned long long)s);
-}
-
-// one key per index position i, as k_poly_edges of polygons.hip:
-// (min << 32) | (max << 1) | (from > to), and the polygon that uses it (pol
-// may be null: the holes need the keys alone)
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_topo_edges(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n, int64_t V,
-             int64_t* __restrict__ ctr, uint64_t* __restrict__ keys, int32_t* __restrict__ pol) {
-  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  int64_t a, b;
-  bool b_ok;
-  uint64_t key = 0;
-  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok) && b_ok) {
-    const uint64_t lo = (uint64_t)(a < b ? a : b), hi = (uint64_t)(a < b ? b : a);
-    key = (lo << 32) | (hi << 1) | (a > b ? 1u : 0u);
-  }
-  keys[i] = key;
-  if (pol) pol[i] = (int32_t)soup_polygon_of(off, P, i);
 }
 
 __global__ void __launch_bounds__(TNP_BLOCK) k_iota(int* __restrict__ a, int64_t n) {
@@ -219,96 +198,18 @@ k_seg_final(const int64_t* __restrict__ start, int64_t nseg, int64_t n, const do
   }
 }
 
-// device scratch of one build, freed on the stream on every way out.  The
-// build reserves two blocks (before and after the class counts are known) and
-// carves its arrays out of them: a stream-ordered allocation that the pool
-// cannot serve from memory it still holds costs more than most of the kernels
-// here, and a build has some forty arrays.  An array that does not fit its
-// block gets an allocation of its own.
-struct Scratch {
-  hipStream_t s;
-  const char* who;
-  std::vector<void*> p;
-  char* cur = nullptr;
-  size_t left = 0;
-  explicit Scratch(hipStream_t st, const char* w = "topology") : s(st), who(w) {}
-  ~Scratch() {
-    for (void* q : p) (void)hipFreeAsync(q, s);
-  }
-  static size_t pad(size_t bytes) { return ((bytes < 256 ? 256 : bytes) + 255) / 256 * 256; }
-  bool reserve(size_t bytes) {
-    cur = nullptr, left = 0;
-    void* q = alloc(bytes);
-    if (!q) return false;
-    cur = static_cast<char*>(q), left = pad(bytes);
-    return true;
-  }
-  void* get(size_t bytes) {
-    const size_t b = pad(bytes);
-    if (b <= left) {
-      void* q = cur;
-      cur += b, left -= b;
-      return q;
-    }
-    return alloc(bytes);
-  }
-  void* alloc(size_t bytes) {
-    void* q = nullptr;
-    if (hipMallocAsync(&q, bytes < 256 ? 256 : bytes, s) != hipSuccess) {
-      tnp_set_error("%s: hipMallocAsync of %zu bytes failed", who, bytes);
-      return nullptr;
-    }
-    p.push_back(q);
-    return q;
-  }
-  template <typename T>
-  T* arr(int64_t n) { return static_cast<T*>(get((size_t)(n > 0 ? n : 1) * sizeof(T))); }
-};
-
-// look-back state of one stand-alone scan launch (zeroed words, epoch 1)
-int scan_flags(Scratch& scr, const int32_t* flag, int64_t n, int64_t* rank, int64_t* total, hipStream_t s) {
-  const size_t words = (size_t)scan_tiles(n) + 1;
-  uint64_t* buf = scr.arr<uint64_t>((int64_t)words);
-  if (!buf) return -1;
-  TNP_CHECK(hipMemsetAsync(buf, 0, words * sizeof(uint64_t), s));
-  TnpLB lb{};
-  lb.ticket = reinterpret_cast<unsigned long long*>(buf);
-  lb.st = buf + 1;
-  lb.tbase = 0;
-  lb.epoch = 1;
-  lb.spin = -1;
-  lb.rc = nullptr;
-  return scan_i32_to_i64(flag, rank, n, total, lb, s);
+// The boundary graph's classes over the sorted keys sk: vparent (any
+// contents) becomes the union-find of the vertices joined by an edge used
+// once, bdeg (zeroed by the caller) their boundary degrees, vrank the number
+// of the class of every root that carries a boundary edge -- the loop numbers
+// -- with their count in ctr[TC_L] and the edges' in ctr[TC_B] (both zero
+// before).  Nothing is read back here.
+int boundary_classes(Scratch& scr, const uint64_t* sk, int64_t n, int64_t V, int* vparent, int* bdeg, int32_t* vflag,
+                     int64_t* vrank, int64_t* ctr, hipStream_t s) {
+  SOUP_LAUNCH(k_iota, V, vparent, V);
+  SOUP_LAUNCH(k_boundary_union, n, sk, n, vparent, bdeg, ctr);
+  SOUP_LAUNCH(k_flag_roots, V, vparent, bdeg, V, vflag);
+  return scan_flags(scr, vflag, V, vrank, ctr + TC_L, s);
 }
-
-int bits_for(int64_t n) {  // the smallest b >= 1 with 2^b >= n
-  int b = 1;
-  while (((int64_t)1 << b) < n) ++b;
-  return b;
-}
-
-// the stage events of a timed build
-struct Stages {
-  bool on;
-  hipStream_t s;
-  std::vector<hipEvent_t> ev;
-  Stages(bool o, hipStream_t st) : on(o), s(st) {}
-  ~Stages() {
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
-  }
-  void mark() {
-    if (!on) return;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) { on = false; return; }
-    (void)hipEventRecord(e, s);
-    ev.push_back(e);
-  }
-};
-
-#define TOPO_LAUNCH(kernel, count, ...)                                                              \
-  do {                                                                                                \
-    hipLaunchKernelGGL(kernel, dim3(tnp_grid(count)), dim3(TNP_BLOCK), 0, s, __VA_ARGS__);           \
-    TNP_CHECK(hipGetLastError());                                                                     \
-  } while (0)
 
 }  // namespace

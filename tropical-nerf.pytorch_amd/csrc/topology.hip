@@ -3,10 +3,9 @@
 // scratch is allocated per build on the caller's stream and freed; the handle
 // keeps the three result tables.
 //
-//   k_soup_offsets    (soup_check.h) the offsets are checked
-//   k_topo_edges      per index: ids checked, one directed-edge key (the
-//                     report's) and its polygon written -- nothing is loaded
-//                     through an id
+//   k_soup_offsets, k_soup_edges   (soup_check.h, behind soup_host.h's front)
+//                     the offsets checked; per index: ids checked, one
+//                     directed-edge key (the report's) and its polygon written
 //   sort_pairs_u64    (key, polygon) on the bits the ids need
 //   k_union_edges     lock-free union-find over the polygons: every use of an
 //                     undirected edge is united with the use before it in the
@@ -34,8 +33,9 @@
 //   k_comp_rows, k_loop_rows    the tables
 // The number of launches is fixed (it does not depend on the graph), and no
 // kernel waits for another workgroup: a failed hook is retried from the new
-// root.  The union-find, the front half's kernels, the segmented sums and the
-// scratch are topo_common.h's, shared with holes.hip.
+// root.  The union-find, the boundary graph's classes and the segmented sums
+// are topo_common.h's, shared with holes.hip.  tnp_topology_build is its
+// stages in order, one function each, with the build's state in a TopoBuild.
 #include <string.h>
 
 #include <algorithm>
@@ -336,75 +336,37 @@ void drop_tables(tnp_topology* t) {
   t->P = t->C = t->L = 0;
 }
 
-}  // namespace
+// the state of one build, handed from stage to stage
+struct TopoBuild {
+  tnp_topology* t;
+  const float* xyz;
+  int64_t V;
+  const int64_t *off, *idx;
+  int64_t P;
+  int connect;
+  hipStream_t s;
+  Scratch scr;
+  Stages st;
+  int64_t* ctr = nullptr;
+  int64_t n = 0, C = 0, L = 0, B = 0;
+  int vbits = 0, pbits = 0, nbits = 0, cbits = 0, lbits = 0;
+  uint64_t *sk = nullptr, *spare = nullptr;  // the sorted keys; n words free once they are sorted
+  int32_t* sp = nullptr;                     // the sorted keys' polygons
+  int *parent = nullptr, *vparent = nullptr, *bdeg = nullptr;
+  int64_t *prank = nullptr, *vrank = nullptr;
+  int64_t *cnt = nullptr, *cstart = nullptr;
+  uint32_t* box = nullptr;
+  double *csum = nullptr, *parea = nullptr, *pdet = nullptr, *pieces = nullptr;
+  size_t vsort_bytes = 0, psort_bytes = 0, lsort_bytes = 0;
+  int edges(), classes(), tables(), components(), loops();  // the stages, in order
+};
 
-extern "C" int tnp_topology_create(tnp_topology** out, int device) {
-  if (!out) { tnp_set_error("topology: null handle pointer"); return -1; }
-  TNP_CHECK(hipSetDevice(device));
-  tnp_topology* t = new tnp_topology();
-  t->device = device;
-  *out = t;
-  return 0;
-}
-
-extern "C" void tnp_topology_destroy(tnp_topology* t) {
-  if (!t) return;
-  (void)hipSetDevice(t->device);
-  drop_tables(t);
-  delete t;
-}
-
-extern "C" int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n) {
-  if (!t) { tnp_set_error("topology: null handle"); return -1; }
-  t->timed = enable != 0;
-  if (ms)
-    for (int i = 0; i < n && i < TNP_TOPOLOGY_STAGES; ++i) ms[i] = i < t->n_ms ? t->ms[i] : 0.0;
-  return TNP_TOPOLOGY_STAGES;
-}
-
-extern "C" int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V, const int64_t* d_offsets,
-                                  const int64_t* d_indices, int64_t P, int connect, int64_t* n_components,
-                                  int64_t* n_loops, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  if (!t) { tnp_set_error("topology: null handle"); return -1; }
-  if (n_components) *n_components = 0;
-  if (n_loops) *n_loops = 0;
-  TNP_CHECK(hipSetDevice(t->device));
-  TNP_CHECK(hipStreamSynchronize(s));  // (an earlier export may still read the tables)
-  drop_tables(t);
-  t->n_ms = 0;
-  if (connect != 0 && connect != 1) { tnp_set_error("topology: connect = %d (0: edge, 1: vertex)", connect); return -1; }
-  if (P < 0 || V < 0) { tnp_set_error("topology: P = %lld, V = %lld", (long long)P, (long long)V); return -1; }
-  if (V >= (int64_t)1 << 31) {
-    tnp_set_error("topology: V = %lld vertices; the edge keys hold ids below 2^31", (long long)V);
-    return -1;
-  }
-  if (P >= (int64_t)1 << 31) {
-    tnp_set_error("topology: P = %lld polygons; the labels hold ids below 2^31", (long long)P);
-    return -1;
-  }
-  if (P == 0) return 0;
-  if (!d_offsets || !d_indices || (V > 0 && !d_xyz)) { tnp_set_error("topology: null array"); return -1; }
-  Scratch scr(s);
-  Stages st(t->timed, s);
-  st.mark();
-
-  // ---- checks, edge keys ----
-  int64_t* ctr = scr.arr<int64_t>(TC_N);
-  if (!ctr) return -1;
-  int64_t h[TC_N];
-  for (int i = 0; i < TC_N; ++i) h[i] = 0;
-  h[TC_ERR] = (int64_t)SOUP_NONE;
-  TNP_CHECK(hipMemcpyAsync(ctr, h, sizeof(h), hipMemcpyHostToDevice, s));
-  TOPO_LAUNCH(k_soup_offsets, P, d_offsets, P, ctr, (int32_t*)nullptr);
-  TNP_CHECK(hipMemcpyAsync(h, ctr, 2 * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[TC_ERR] != SOUP_NONE)
-    return soup_report_error("topology", (unsigned long long)h[TC_ERR], d_offsets, d_indices, V, s);
-  const int64_t n = h[TC_NIDX];  // >= 3 P: every offset is now known to lie in [0, n]
-  const int vbits = bits_for(V), pbits = bits_for(P), nbits = bits_for(n);
+// stages check_edges, edge_sort
+int TopoBuild::edges() {
+  n = soup_offsets("topology", scr, off, idx, V, P, &ctr, TC_N, s);
+  if (n < 0) return -1;
+  vbits = bits_for(V), pbits = bits_for(P), nbits = bits_for(n);
   const int key_bits = 32 + vbits;
-
   const size_t pair_bytes = sort_pairs_u64_scratch_bytes(n, key_bits);
   {  // everything up to the class counts
     const size_t scan_words = (size_t)scan_tiles(P) + (size_t)scan_tiles(V) + 2;
@@ -420,70 +382,68 @@ extern "C" int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V
   int32_t* pb = scr.arr<int32_t>(n);
   void* pair_scr = scr.get(pair_bytes);
   if (!ka || !kb || !pa || !pb || !pair_scr) return -1;
-  TOPO_LAUNCH(k_topo_edges, n, d_offsets, P, d_indices, n, V, ctr, ka, pa);
+  SOUP_LAUNCH((k_soup_edges<false, true>), n, off, P, idx, n, V, ctr, ka, (uint8_t*)nullptr, pa);
   // the ids are read through from here on: the check's verdict first
-  TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(int64_t), hipMemcpyDeviceToHost, s));
-  TNP_CHECK(hipStreamSynchronize(s));
-  if ((unsigned long long)h[TC_ERR] != SOUP_NONE)
-    return soup_report_error("topology", (unsigned long long)h[TC_ERR], d_offsets, d_indices, V, s);
+  int64_t h[1];
+  if (soup_verdict("topology", off, idx, V, ctr, h, 1, s)) return -1;
   st.mark();
-
-  uint64_t* sk = nullptr;
-  int32_t* sp = nullptr;
   if (sort_pairs_u64(ka, kb, pa, pb, n, key_bits, pair_scr, pair_bytes, &sk, &sp, s)) return -1;
-  uint64_t* spare = sk == ka ? kb : ka;  // n words, free from here on
+  spare = sk == ka ? kb : ka;
   st.mark();
+  return 0;
+}
 
-  // ---- the polygons' classes ----
-  int* parent = scr.arr<int>(P);
+// stages label_polygons, label_boundary: the classes and their counts C, L, B
+int TopoBuild::classes() {
+  parent = scr.arr<int>(P);
   int32_t* pflag = scr.arr<int32_t>(P);
-  int64_t* prank = scr.arr<int64_t>(P);
+  prank = scr.arr<int64_t>(P);
   if (!parent || !pflag || !prank) return -1;
-  TOPO_LAUNCH(k_iota, P, parent, P);
+  SOUP_LAUNCH(k_iota, P, parent, P);
   if (connect == 0) {
-    TOPO_LAUNCH(k_union_edges, n, sk, sp, n, parent);
+    SOUP_LAUNCH(k_union_edges, n, sk, sp, n, parent);
   } else {
     unsigned* vown = scr.arr<unsigned>(V);
     if (!vown) return -1;
     TNP_CHECK(hipMemsetAsync(vown, 0xFF, (size_t)V * sizeof(unsigned), s));
-    TOPO_LAUNCH(k_vertex_owner, n, d_offsets, P, d_indices, n, vown);
-    TOPO_LAUNCH(k_union_vertices, n, d_offsets, P, d_indices, n, vown, parent);
+    SOUP_LAUNCH(k_vertex_owner, n, off, P, idx, n, vown);
+    SOUP_LAUNCH(k_union_vertices, n, off, P, idx, n, vown, parent);
   }
-  TOPO_LAUNCH(k_flag_roots, P, parent, (const int*)nullptr, P, pflag);
+  SOUP_LAUNCH(k_flag_roots, P, parent, (const int*)nullptr, P, pflag);
   if (scan_flags(scr, pflag, P, prank, ctr + TC_C, s)) return -1;
   st.mark();
 
-  // ---- the boundary graph's classes ----
-  int* vparent = scr.arr<int>(V);
-  int* bdeg = scr.arr<int>(V);
+  vparent = scr.arr<int>(V);
+  bdeg = scr.arr<int>(V);
   int32_t* vflag = scr.arr<int32_t>(V);
-  int64_t* vrank = scr.arr<int64_t>(V);
+  vrank = scr.arr<int64_t>(V);
   if (!vparent || !bdeg || !vflag || !vrank) return -1;
-  TOPO_LAUNCH(k_iota, V, vparent, V);
   TNP_CHECK(hipMemsetAsync(bdeg, 0, (size_t)(V > 0 ? V : 1) * sizeof(int), s));
-  TOPO_LAUNCH(k_boundary_union, n, sk, n, vparent, bdeg, ctr);
-  TOPO_LAUNCH(k_flag_roots, V, vparent, bdeg, V, vflag);
-  if (scan_flags(scr, vflag, V, vrank, ctr + TC_L, s)) return -1;
+  if (boundary_classes(scr, sk, n, V, vparent, bdeg, vflag, vrank, ctr, s)) return -1;
+  int64_t h[TC_N];
   TNP_CHECK(hipMemcpyAsync(h, ctr, sizeof(h), hipMemcpyDeviceToHost, s));
   TNP_CHECK(hipStreamSynchronize(s));
   st.mark();
-  const int64_t C = h[TC_C], L = h[TC_L], B = h[TC_B];
+  C = h[TC_C], L = h[TC_L], B = h[TC_B];
   if (C < 1 || C > P || L < 0 || L > B) {
     tnp_set_error("topology: %lld components of %lld polygons, %lld loops of %lld boundary edges",
                   (long long)C, (long long)P, (long long)L, (long long)B);
     return -1;
   }
-  const int cbits = bits_for(C), lbits = bits_for(L);
+  cbits = bits_for(C), lbits = bits_for(L);
   if (lbits + nbits > 64) { tnp_set_error("topology: %lld loops over %lld indices do not fit a key", (long long)L, (long long)n); return -1; }
+  return 0;
+}
 
-  // ---- the tables ----
+// stage tables_alloc: the handle's tables, the second scratch block, the per-component accumulators cleared
+int TopoBuild::tables() {
   TNP_CHECK(hipMalloc(&t->label, (size_t)P * sizeof(int32_t)));
   TNP_CHECK(hipMalloc(&t->comps, (size_t)C * sizeof(tnp_component)));
   if (L > 0) TNP_CHECK(hipMalloc(&t->loops, (size_t)L * sizeof(tnp_boundary_loop)));
-  const size_t vsort_bytes = sort_scratch_bytes(n, vbits + cbits);
-  const size_t psort_bytes = sort_scratch_bytes(P, pbits + cbits);
-  const size_t lsort_bytes = L > 0 ? sort_scratch_bytes(B, lbits + nbits) : 0;
-  {  // everything after them
+  vsort_bytes = sort_scratch_bytes(n, vbits + cbits);
+  psort_bytes = sort_scratch_bytes(P, pbits + cbits);
+  lsort_bytes = L > 0 ? sort_scratch_bytes(B, lbits + nbits) : 0;
+  {  // everything after the class counts
     const size_t need = Scratch::pad(CK_N * C * sizeof(int64_t)) + Scratch::pad(6 * C * sizeof(uint32_t)) +
                         Scratch::pad((C + 1) * sizeof(int64_t)) + Scratch::pad(2 * C * sizeof(double)) +
                         2 * Scratch::pad(P * sizeof(double)) + Scratch::pad(2 * std::max(P, B) * sizeof(double)) +
@@ -494,112 +454,130 @@ extern "C" int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V
                         Scratch::pad(lsort_bytes) + Scratch::pad(sizeof(unsigned long long));
     if (!scr.reserve(need)) return -1;
   }
-  int64_t* cnt = scr.arr<int64_t>(CK_N * C);
-  uint32_t* box = scr.arr<uint32_t>(6 * C);
-  int64_t* cstart = scr.arr<int64_t>(C + 1);
-  double* csum = scr.arr<double>(2 * C);
-  double* parea = scr.arr<double>(P);
-  double* pdet = scr.arr<double>(P);
-  double* pieces = scr.arr<double>(2 * std::max(P, B));
+  cnt = scr.arr<int64_t>(CK_N * C);
+  box = scr.arr<uint32_t>(6 * C);
+  cstart = scr.arr<int64_t>(C + 1);
+  csum = scr.arr<double>(2 * C);
+  parea = scr.arr<double>(P);
+  pdet = scr.arr<double>(P);
+  pieces = scr.arr<double>(2 * std::max(P, B));
   if (!cnt || !box || !cstart || !csum || !parea || !pdet || !pieces) return -1;
-  {
-    FillOp ops[3] = {{cnt, (uint64_t)(CK_N * C) * sizeof(int64_t), 0u},
-                     {box, (uint64_t)(3 * C) * sizeof(uint32_t), 0xFFu},
-                     {box + 3 * C, (uint64_t)(3 * C) * sizeof(uint32_t), 0u}};
-    if (launch_fill(ops, 3, s)) return -1;
-  }
+  FillOp ops[3] = {{cnt, (uint64_t)(CK_N * C) * sizeof(int64_t), 0u},
+                   {box, (uint64_t)(3 * C) * sizeof(uint32_t), 0xFFu},
+                   {box + 3 * C, (uint64_t)(3 * C) * sizeof(uint32_t), 0u}};
+  if (launch_fill(ops, 3, s)) return -1;
+  st.mark();
+  return 0;
+}
+
+// stages component_counts, vertex_sort, polygon_order, geometry: the labels and the component rows
+int TopoBuild::components() {
+  SOUP_LAUNCH(k_labels, P, parent, prank, P, t->label, cnt, C);
+  SOUP_LAUNCH(k_comp_polys, P, xyz, off, idx, P, t->label, cnt, box, C, parea, pdet);
+  SOUP_LAUNCH(k_edge_stats, n, sk, sp, n, t->label, cnt, C);
   st.mark();
 
-  // ---- labels, per-component counts ----
-  TOPO_LAUNCH(k_labels, P, parent, prank, P, t->label, cnt, C);
-  TOPO_LAUNCH(k_comp_polys, P, d_xyz, d_offsets, d_indices, P, t->label, cnt, box, C, parea, pdet);
-  TOPO_LAUNCH(k_edge_stats, n, sk, sp, n, t->label, cnt, C);
-  st.mark();
-
-  // ---- distinct (label, vertex) ----
-  {
-    const int bits = vbits + cbits;
-    const size_t bytes = vsort_bytes;
+  {  // distinct (label, vertex)
     uint64_t* va = spare;
     uint64_t* vb = scr.arr<uint64_t>(n);
-    void* sscr = scr.get(bytes);
+    void* sscr = scr.get(vsort_bytes);
     if (!vb || !sscr) return -1;
-    TOPO_LAUNCH(k_vertex_keys, n, d_offsets, P, d_indices, n, t->label, vbits, va);
+    SOUP_LAUNCH(k_vertex_keys, n, off, P, idx, n, t->label, vbits, va);
     uint64_t* sv = nullptr;
-    if (sort_keys_u64(va, vb, n, bits, sscr, bytes, &sv, s)) return -1;
-    TOPO_LAUNCH(k_key_runs, n, sv, n, vbits, cnt + CK_NVERT * C);
+    if (sort_keys_u64(va, vb, n, vbits + cbits, sscr, vsort_bytes, &sv, s)) return -1;
+    SOUP_LAUNCH(k_key_runs, n, sv, n, vbits, cnt + CK_NVERT * C);
   }
   st.mark();
 
-  // ---- the polygons in (label, p) order ----
+  // the polygons in (label, p) order
   uint64_t* spk = nullptr;
-  {
-    const int bits = pbits + cbits;
-    const size_t bytes = psort_bytes;
-    uint64_t* qa = scr.arr<uint64_t>(P);
-    uint64_t* qb = scr.arr<uint64_t>(P);
-    void* sscr = scr.get(bytes);
-    if (!qa || !qb || !sscr) return -1;
-    TOPO_LAUNCH(k_poly_keys, P, t->label, P, pbits, qa);
-    if (sort_keys_u64(qa, qb, P, bits, sscr, bytes, &spk, s)) return -1;
-    TOPO_LAUNCH(k_seg_starts, P, spk, P, pbits, C, cstart);
-  }
+  uint64_t* qa = scr.arr<uint64_t>(P);
+  uint64_t* qb = scr.arr<uint64_t>(P);
+  void* sscr = scr.get(psort_bytes);
+  if (!qa || !qb || !sscr) return -1;
+  SOUP_LAUNCH(k_poly_keys, P, t->label, P, pbits, qa);
+  if (sort_keys_u64(qa, qb, P, pbits + cbits, sscr, psort_bytes, &spk, s)) return -1;
+  SOUP_LAUNCH(k_seg_starts, P, spk, P, pbits, C, cstart);
   st.mark();
 
-  // ---- area, volume ----
+  // area, volume
   hipLaunchKernelGGL((k_seg_pieces<2, PolyVals>), dim3(tnp_grid(P, SEG)), dim3(TNP_BLOCK), 0, s, spk, P, pbits,
                      PolyVals{parea, pdet}, pieces);
-  hipLaunchKernelGGL(k_seg_final<2>, dim3(tnp_grid(C, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, cstart, C, P, pieces, csum);
+  hipLaunchKernelGGL(k_seg_final<2>, dim3(tnp_grid(C, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, cstart, C, P, pieces,
+                     csum);
   TNP_CHECK(hipGetLastError());
-  TOPO_LAUNCH(k_comp_rows, C, C, cnt, cstart, box, csum, t->comps);
+  SOUP_LAUNCH(k_comp_rows, C, C, cnt, cstart, box, csum, t->comps);
   st.mark();
+  return 0;
+}
 
-  // ---- the loops ----
+// stage loops: the loop rows
+int TopoBuild::loops() {
   if (L > 0) {
-    const int bits = lbits + nbits;
-    const size_t bytes = lsort_bytes;
     int64_t* lcnt = scr.arr<int64_t>(LK_N * L);
     int64_t* lstart = scr.arr<int64_t>(L + 1);
     double* llen = scr.arr<double>(L);
     uint64_t* la = scr.arr<uint64_t>(B);
     uint64_t* lb = scr.arr<uint64_t>(B);
-    void* sscr = scr.get(bytes);
+    void* sscr = scr.get(lsort_bytes);
     unsigned long long* cur = scr.arr<unsigned long long>(1);
     if (!lcnt || !lstart || !llen || !la || !lb || !sscr || !cur) return -1;
     TNP_CHECK(hipMemsetAsync(lcnt, 0, (size_t)(LK_N * L) * sizeof(int64_t), s));
     TNP_CHECK(hipMemsetAsync(cur, 0, sizeof(unsigned long long), s));
-    TOPO_LAUNCH(k_loop_verts, V, vparent, bdeg, vrank, V, lcnt, L);
-    TOPO_LAUNCH(k_loop_keys, n, sk, n, vparent, vrank, nbits, la, B, cur);
+    SOUP_LAUNCH(k_loop_verts, V, vparent, bdeg, vrank, V, lcnt, L);
+    SOUP_LAUNCH(k_loop_keys, n, sk, n, vparent, vrank, nbits, la, B, cur);
     uint64_t* sl = nullptr;
-    if (sort_keys_u64(la, lb, B, bits, sscr, bytes, &sl, s)) return -1;
-    TOPO_LAUNCH(k_seg_starts, B, sl, B, nbits, L, lstart);
+    if (sort_keys_u64(la, lb, B, lbits + nbits, sscr, lsort_bytes, &sl, s)) return -1;
+    SOUP_LAUNCH(k_seg_starts, B, sl, B, nbits, L, lstart);
     hipLaunchKernelGGL((k_seg_pieces<1, EdgeLength>), dim3(tnp_grid(B, SEG)), dim3(TNP_BLOCK), 0, s, sl, B, nbits,
-                       EdgeLength{sk, d_xyz}, pieces);
-    hipLaunchKernelGGL(k_seg_final<1>, dim3(tnp_grid(L, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, lstart, L, B, pieces, llen);
+                       EdgeLength{sk, xyz}, pieces);
+    hipLaunchKernelGGL(k_seg_final<1>, dim3(tnp_grid(L, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, lstart, L, B, pieces,
+                       llen);
     TNP_CHECK(hipGetLastError());
-    TOPO_LAUNCH(k_loop_rows, L, L, lcnt, lstart, sl, nbits, sp, t->label, llen, t->loops);
+    SOUP_LAUNCH(k_loop_rows, L, L, lcnt, lstart, sl, nbits, sp, t->label, llen, t->loops);
   }
   st.mark();
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int tnp_topology_create(tnp_topology** out, int device) { return handle_create("topology", out, device); }
+
+extern "C" void tnp_topology_destroy(tnp_topology* t) { handle_destroy(t, drop_tables); }
+
+extern "C" int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n) {
+  return handle_stages("topology", t, enable, ms, n);
+}
+
+extern "C" int tnp_topology_build(tnp_topology* t, const float* d_xyz, int64_t V, const int64_t* d_offsets,
+                                  const int64_t* d_indices, int64_t P, int connect, int64_t* n_components,
+                                  int64_t* n_loops, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
+  if (n_components) *n_components = 0;
+  if (n_loops) *n_loops = 0;
+  if (handle_use("topology", t)) return -1;
+  TNP_CHECK(hipStreamSynchronize(s));  // (an earlier export may still read the tables)
+  drop_tables(t);
+  t->n_ms = 0;
+  if (connect != 0 && connect != 1) { tnp_set_error("topology: connect = %d (0: edge, 1: vertex)", connect); return -1; }
+  if (soup_args("topology", V, P, true, P > 0, d_xyz, d_offsets, d_indices)) return -1;
+  if (P == 0) return 0;
+  TopoBuild b{t, d_xyz, V, d_offsets, d_indices, P, connect, s, Scratch(s, "topology"), Stages(t->timed, s)};
+  b.st.mark();
+  if (b.edges() || b.classes() || b.tables() || b.components() || b.loops()) return -1;
   TNP_CHECK(hipStreamSynchronize(s));
-  t->P = P, t->C = C, t->L = L;
-  if (st.on && (int)st.ev.size() == TNP_TOPOLOGY_STAGES + 1) {
-    for (int i = 0; i < TNP_TOPOLOGY_STAGES; ++i) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, st.ev[i], st.ev[i + 1]);
-      t->ms[i] = (double)ms;
-    }
-    t->n_ms = TNP_TOPOLOGY_STAGES;
-  }
-  if (n_components) *n_components = C;
-  if (n_loops) *n_loops = L;
+  t->P = P, t->C = b.C, t->L = b.L;
+  handle_keep_ms(t, b.st);
+  if (n_components) *n_components = b.C;
+  if (n_loops) *n_loops = b.L;
   return 0;
 }
 
 extern "C" int tnp_topology_export(tnp_topology* t, int32_t* d_label, tnp_component* d_components,
                                    tnp_boundary_loop* d_loops, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  if (!t) { tnp_set_error("topology: null handle"); return -1; }
-  TNP_CHECK(hipSetDevice(t->device));
+  if (handle_use("topology", t)) return -1;
   if (d_label && t->P > 0)
     TNP_CHECK(hipMemcpyAsync(d_label, t->label, (size_t)t->P * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
   if (d_components && t->C > 0)

@@ -159,18 +159,9 @@ def polygon_report(vertices, offsets, indices, per_polygon: bool = False) -> dic
     import torch
 
     from .. import _hip
-    dev = torch.device("cuda", torch.cuda.current_device())
-
-    def t(x, dtype):
-        x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(dev, dtype).contiguous()
-
-    v, off, idx = t(vertices, torch.float32).reshape(-1, 3), t(offsets, torch.int64), t(indices, torch.int64)
-    P = off.numel() - 1
-    if P < 0:
-        raise ValueError("offsets holds P + 1 entries")
-    if P > 0 and idx.numel() < int(off[-1]):  # (the library reads indices[:offsets[-1]])
-        raise ValueError(f"offsets end at {int(off[-1])}, only {idx.numel()} indices given")
+    from .soup import current_device, soup_on_device
+    dev = current_device()
+    v, off, idx, P = soup_on_device(vertices, offsets, indices, dev)
     area = torch.empty(P, device=dev) if per_polygon else None
     devi = torch.empty(P, device=dev) if per_polygon else None
     st = _hip.TnpPolygonStats()

@@ -18,6 +18,7 @@ import torch
 from .. import _hip
 from .colormap import lut as _lut
 from .mesh import Mesh, PolygonMesh
+from .soup import current_device, soup_on_device, to_device
 
 _AXES = {"x": 0, "y": 1, "z": 2}
 EDGE_RGBA = (0, 0, 0, 255)
@@ -96,10 +97,6 @@ class Camera:
 
 def _soup(mesh, dev):
     """(vertices fp32 [V, 3], offsets int64 [P + 1], indices int64, normals or None) on the device."""
-    def t(x, dtype):
-        x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(dev, dtype).contiguous()
-
     normals = None
     if isinstance(mesh, PolygonMesh):
         v, off, idx, normals = mesh.vertices, mesh.offsets, mesh.indices, mesh.normals
@@ -112,13 +109,11 @@ def _soup(mesh, dev):
         normals = mesh[3] if len(mesh) == 4 else None
     else:
         raise TypeError("render: a Mesh, a PolygonMesh, (vertices, faces) or (vertices, offsets, indices[, normals])")
-    v, idx = t(v, torch.float32).reshape(-1, 3), t(idx, torch.int64).reshape(-1)
-    off = torch.arange(0, idx.numel() + 1, 3, device=dev) if off is None else t(off, torch.int64).reshape(-1)
-    if off.numel() < 1:
-        raise ValueError("render: offsets holds P + 1 entries")
-    if off.numel() > 1 and idx.numel() < int(off[-1]):  # (the library reads indices[:offsets[-1]])
-        raise ValueError(f"render: offsets end at {int(off[-1])}, only {idx.numel()} indices given")
-    return v, off, idx, (None if normals is None else t(normals, torch.float32).reshape(-1, 3))
+    if off is None:
+        idx = to_device(idx, dev, torch.int64)
+        off = torch.arange(0, idx.numel() + 1, 3, device=dev)
+    v, off, idx, _ = soup_on_device(v, off, idx, dev, "render: ")
+    return v, off, idx, (None if normals is None else to_device(normals, dev, torch.float32).reshape(-1, 3))
 
 
 def newell_normals(v: torch.Tensor, off: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
@@ -141,7 +136,7 @@ def rasterize(mesh, camera: Camera, size, scale_by: int = 1, edge_half_width: in
     tensors ``prim`` (int32 [H, W] polygon id, -1 background), ``tri`` (the
     winning fan triangle), ``edge`` (uint8 mask), optionally ``screen``
     ([V, 3] int32), and ``stats``."""
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = current_device()
     v, off, idx, _ = _soup(mesh, dev)  # (tensors already in place pass through unchanged)
     W, H = int(size[0]), int(size[1])
     ok = 1 <= W <= 8192 and 1 <= H <= 8192  # (the library refuses; nothing is allocated for a bad size)
@@ -192,7 +187,7 @@ def render(mesh, camera: Camera, size=(1024, 1024), ssaa: int = 1, edges: bool =
     vmin="auto" maps min..max as the reference's Normalize() does.
     cmap: "plasma", "gray" or a [256, 3] uint8 table.
     return_buffers: also return rasterize()'s dict (at the raster's size)."""
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = current_device()
     if ssaa not in (1, 2, 4):
         raise ValueError(f"ssaa = {ssaa} (1, 2, 4)")
     v, off, idx, normals = _soup(mesh, dev)

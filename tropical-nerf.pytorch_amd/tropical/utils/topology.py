@@ -20,6 +20,7 @@ import ctypes as C
 import numpy as np
 
 from .mesh import PolygonMesh
+from .soup import Handle, current_device, soup_on_device, stage_ms, to_device
 
 # the rows of tnp_component / tnp_boundary_loop
 COMPONENT_DTYPE = np.dtype([(k, "<i8") for k in ("first_polygon", "n_polygons", "n_indices", "n_vertices", "n_edges",
@@ -56,26 +57,8 @@ class PolygonTopology:
         return len(self.loops)
 
 
-class _Handle:
-    def __init__(self, dev):
-        from .. import _hip
-        self._hip, self.h = _hip, C.c_void_p()
-        _hip.check(_hip.lib().tnp_topology_create(C.byref(self.h), dev.index), "tnp_topology_create")
-
-    def close(self):
-        if self.h:
-            self._hip.lib().tnp_topology_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def polygon_topology(vertices, offsets, indices, connect: str = "edge", timed: bool = False,
-                     handle: "_Handle | None" = None) -> PolygonTopology:
+                     handle: "Handle | None" = None) -> PolygonTopology:
     """Label the components of a polygon soup and trace its boundary loops
     (tnp_topology_build / tnp_topology_export).  connect: "edge" (polygons
     sharing an undirected edge) or "vertex" (sharing a vertex id).  numpy
@@ -88,20 +71,10 @@ def polygon_topology(vertices, offsets, indices, connect: str = "edge", timed: b
     from .. import _hip
     if connect not in CONNECT:
         raise ValueError(f"connect = {connect!r} (edge, vertex)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-
-    def t(x, dtype):
-        x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-        return x.to(dev, dtype).contiguous()
-
-    v, off, idx = t(vertices, torch.float32).reshape(-1, 3), t(offsets, torch.int64), t(indices, torch.int64)
-    P = off.numel() - 1
-    if P < 0:
-        raise ValueError("offsets holds P + 1 entries")
-    if P > 0 and idx.numel() < int(off[-1]):  # (the library reads indices[:offsets[-1]])
-        raise ValueError(f"offsets end at {int(off[-1])}, only {idx.numel()} indices given")
+    dev = current_device()
+    v, off, idx, P = soup_on_device(vertices, offsets, indices, dev)
     own = handle is None
-    hd = _Handle(dev) if own else handle
+    hd = _topology_handle(dev) if own else handle
     try:
         lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(dev))
         if timed:
@@ -114,24 +87,27 @@ def polygon_topology(vertices, offsets, indices, connect: str = "edge", timed: b
         loops = torch.empty(nl.value * LOOP_DTYPE.itemsize, dtype=torch.uint8, device=dev)
         _hip.check(lib.tnp_topology_export(hd.h, _hip.ptr(labels), _hip.ptr(comps), _hip.ptr(loops), stream),
                    "tnp_topology_export")
-        stage_ms = None
-        if timed:
-            ms = (C.c_double * len(STAGES))()
-            lib.tnp_debug_topology_stages(hd.h, 0, ms, len(STAGES))
-            stage_ms = dict(zip(STAGES, (float(x) for x in ms)))
+        times = stage_ms(lib.tnp_debug_topology_stages, hd, STAGES) if timed else None
         comps_h = comps.cpu().numpy().view(COMPONENT_DTYPE).copy()
         loops_h = loops.cpu().numpy().view(LOOP_DTYPE).copy()
     finally:
         if own:
             hd.close()
-    return PolygonTopology(labels, comps_h, loops_h, connect, stage_ms)
+    return PolygonTopology(labels, comps_h, loops_h, connect, times)
 
 
 def topology_handle():
     """A tnp_topology handle on the current device for repeated builds
     (``polygon_topology(..., handle=h)``); ``h.close()`` frees it."""
-    import torch
-    return _Handle(torch.device("cuda", torch.cuda.current_device()))
+    return _topology_handle(current_device())
+
+
+def _topology_handle(dev):
+    return Handle(dev, "tnp_topology_create", "tnp_topology_destroy")
+
+
+def _holes_handle(dev):
+    return Handle(dev, "tnp_holes_create", "tnp_holes_destroy")
 
 
 class BoundaryCycles:
@@ -150,42 +126,19 @@ class BoundaryCycles:
         return len(self.cycle_loop)
 
 
-class _HolesHandle:
-    def __init__(self, dev):
-        from .. import _hip
-        self._hip, self.h = _hip, C.c_void_p()
-        _hip.check(_hip.lib().tnp_holes_create(C.byref(self.h), dev.index), "tnp_holes_create")
-
-    def close(self):
-        if self.h:
-            self._hip.lib().tnp_holes_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
 def holes_handle():
     """A tnp_holes handle on the current device for repeated builds
     (``boundary_cycles(..., handle=h)``); ``h.close()`` frees it."""
-    import torch
-    return _HolesHandle(torch.device("cuda", torch.cuda.current_device()))
+    return _holes_handle(current_device())
 
 
-def _build_cycles(hd, dev, V, off, idx, max_edges, timed=False):
-    """tnp_holes_build + tnp_holes_export on device tensors -> BoundaryCycles."""
+def _build_cycles(hd, dev, V, offsets, indices, max_edges, timed=False):
+    """tnp_holes_build + tnp_holes_export -> BoundaryCycles."""
     import torch
 
     from .. import _hip
     lib, stream = _hip.lib(), C.c_void_p(_hip.stream_ptr(dev))
-    P = off.numel() - 1
-    if P < 0:
-        raise ValueError("offsets holds P + 1 entries")
-    if P > 0 and idx.numel() < int(off[-1]):  # (the library reads indices[:offsets[-1]])
-        raise ValueError(f"offsets end at {int(off[-1])}, only {idx.numel()} indices given")
+    _, off, idx, P = soup_on_device(None, offsets, indices, dev)
     if timed:
         lib.tnp_debug_holes_stages(hd.h, 1, None, 0)
     st = _hip.TnpHoleStats()
@@ -198,13 +151,8 @@ def _build_cycles(hd, dev, V, off, idx, max_edges, timed=False):
     cv = torch.empty(stats["n_cycle_indices"], dtype=torch.int64, device=dev)
     _hip.check(lib.tnp_holes_export(hd.h, _hip.ptr(status), _hip.ptr(loop), _hip.ptr(coff), _hip.ptr(cv), stream),
                "tnp_holes_export")
-    stage_ms = None
-    if timed:
-        ms = (C.c_double * len(HOLE_STAGES))()
-        lib.tnp_debug_holes_stages(hd.h, 0, ms, len(HOLE_STAGES))
-        stage_ms = dict(zip(HOLE_STAGES, (float(x) for x in ms)))
-    return BoundaryCycles(status.cpu().numpy(), loop.cpu().numpy(), coff.cpu().numpy(), cv.cpu().numpy(), stats,
-                          stage_ms)
+    times = stage_ms(lib.tnp_debug_holes_stages, hd, HOLE_STAGES) if timed else None
+    return BoundaryCycles(status.cpu().numpy(), loop.cpu().numpy(), coff.cpu().numpy(), cv.cpu().numpy(), stats, times)
 
 
 def _caps(hd, dev, mode, stats, xyz):
@@ -222,13 +170,7 @@ def _caps(hd, dev, mode, stats, xyz):
     return coff.cpu().numpy(), cidx.cpu().numpy(), new.cpu().numpy()
 
 
-def _to_device(x, dev, dtype):
-    import torch
-    x = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
-    return x.to(dev, dtype).contiguous()
-
-
-def boundary_cycles(vertices, offsets, indices, max_edges: int = 0, handle: "_HolesHandle | None" = None,
+def boundary_cycles(vertices, offsets, indices, max_edges: int = 0, handle: "Handle | None" = None,
                     timed: bool = False) -> BoundaryCycles:
     """The soup's boundary loops, classified and put into cyclic order
     (tnp_holes_build / tnp_holes_export; include/tropical_hip.h has the
@@ -237,32 +179,30 @@ def boundary_cycles(vertices, offsets, indices, max_edges: int = 0, handle: "_Ho
     max_edges > 0 leaves longer loops open.  Malformed input raises
     RuntimeError naming the first offender.  handle: a `holes_handle()` to
     build on (else one is made and closed); its caps are `cycle_caps`'."""
-    import torch
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = current_device()
     V = int(vertices) if np.isscalar(vertices) else int(np.prod(tuple(vertices.shape))) // 3
-    off, idx = _to_device(offsets, dev, torch.int64), _to_device(indices, dev, torch.int64)
     own = handle is None
-    hd = _HolesHandle(dev) if own else handle
+    hd = _holes_handle(dev) if own else handle
     try:
-        return _build_cycles(hd, dev, V, off, idx, max_edges, timed)
+        return _build_cycles(hd, dev, V, offsets, indices, max_edges, timed)
     finally:
         if own:
             hd.close()
 
 
-def cycle_caps(handle: "_HolesHandle", cycles: BoundaryCycles, mode: str = "polygon", vertices=None):
+def cycle_caps(handle: Handle, cycles: BoundaryCycles, mode: str = "polygon", vertices=None):
     """The caps of the build `handle` holds (tnp_holes_caps) as numpy
     ``(offsets, indices, new_vertices)``; mode "star" reads `vertices` (the
     soup's V x 3 coordinates) and returns the fp32 centres it adds."""
     import torch
     if mode not in CAP_MODES:
         raise ValueError(f"mode = {mode!r} (polygon, star)")
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = current_device()
     xyz = None
     if mode == "star":
         if vertices is None:
             raise ValueError("mode = 'star' needs the vertices")
-        xyz = _to_device(vertices, dev, torch.float32).reshape(-1, 3)
+        xyz = to_device(vertices, dev, torch.float32).reshape(-1, 3)
     return _caps(handle, dev, mode, cycles.stats, xyz)
 
 
@@ -305,12 +245,11 @@ def fill_holes(pmesh: PolygonMesh, max_edges: int = 0, mode: str = "polygon"):
     import torch
     if mode not in CAP_MODES:
         raise ValueError(f"mode = {mode!r} (polygon, star)")
-    dev = torch.device("cuda", torch.cuda.current_device())
-    off, idx = _to_device(pmesh.offsets, dev, torch.int64), _to_device(pmesh.indices, dev, torch.int64)
-    xyz = _to_device(pmesh.vertices, dev, torch.float32).reshape(-1, 3) if mode == "star" else None
-    hd = _HolesHandle(dev)
+    dev = current_device()
+    xyz = to_device(pmesh.vertices, dev, torch.float32).reshape(-1, 3) if mode == "star" else None
+    hd = _holes_handle(dev)
     try:
-        cyc = _build_cycles(hd, dev, len(pmesh.vertices), off, idx, max_edges)
+        cyc = _build_cycles(hd, dev, len(pmesh.vertices), pmesh.offsets, pmesh.indices, max_edges)
         coff, cidx, new = _caps(hd, dev, mode, cyc.stats, xyz)
     finally:
         hd.close()
