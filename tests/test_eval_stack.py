@@ -2,12 +2,10 @@
 surface sampling, Chamfer / angular distance, PLY I/O and the train CLI.
 
 CPU: the procedural case table closes and orients surfaces, PLY round trip,
-CLI flags.  GPU: the HIP marching cubes equals the numpy oracle bitwise
-(oracle/marching_cubes.py, same table), the ray caster equals a brute-force
-Moller-Trumbore, nearest neighbours equal numpy, and the CLI runs end to end
-on the stand-in small net.  PyMCubes / cubvh / sklearn (the reference's
-helpers) are absent here: parity with them is unpinned; these tests pin the
-kernels to restatements of the same formulas."""
+CLI flags.  GPU: one case each of marching cubes, the ray caster and nearest
+neighbours against their restatements (test_gpu_eval_kernels.py says what
+they are pinned to and holds them to it at their edges), and the CLI runs end
+to end on the stand-in small net."""
 from collections import Counter
 
 import numpy as np

@@ -190,7 +190,11 @@ __global__ void k_grid_bin(const float* __restrict__ V, const int32_t* __restric
       }
 }
 
-// Moller-Trumbore; t of the hit or +inf
+// Moller-Trumbore; t of the hit or +inf.  det scales with the triangle's area
+// and |dir|, so only det == 0 (ray in the triangle's plane, or a degenerate
+// triangle) is refused: any absolute threshold would make the answer depend on
+// the unit of length.  The tests are written so that a non-finite u, v or t
+// (1 / det overflowing on a denormal det) is a miss too.
 __device__ __forceinline__ float ray_tri(const float o[3], const float dir[3], const float* a,
                                          const float* b, const float* c) {
   const float e1[3] = {b[0] - a[0], b[1] - a[1], b[2] - a[2]};
@@ -198,17 +202,17 @@ __device__ __forceinline__ float ray_tri(const float o[3], const float dir[3], c
   const float p[3] = {dir[1] * e2[2] - dir[2] * e2[1], dir[2] * e2[0] - dir[0] * e2[2],
                       dir[0] * e2[1] - dir[1] * e2[0]};
   const float det = e1[0] * p[0] + e1[1] * p[1] + e1[2] * p[2];
-  if (fabsf(det) < 1e-12f) return INFINITY;
+  if (det == 0.f) return INFINITY;
   const float inv = 1.0f / det;
   const float s[3] = {o[0] - a[0], o[1] - a[1], o[2] - a[2]};
   const float u = (s[0] * p[0] + s[1] * p[1] + s[2] * p[2]) * inv;
-  if (u < 0.f || u > 1.f) return INFINITY;
+  if (!(u >= 0.f && u <= 1.f)) return INFINITY;
   const float q[3] = {s[1] * e1[2] - s[2] * e1[1], s[2] * e1[0] - s[0] * e1[2],
                       s[0] * e1[1] - s[1] * e1[0]};
   const float v = (dir[0] * q[0] + dir[1] * q[1] + dir[2] * q[2]) * inv;
-  if (v < 0.f || u + v > 1.f) return INFINITY;
+  if (!(v >= 0.f && u + v <= 1.f)) return INFINITY;
   const float t = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) * inv;
-  return t > 0.f ? t : INFINITY;
+  return t > 0.f ? t : INFINITY;  // false for a NaN
 }
 
 // 3D DDA through the grid; the nearest hit inside the current cell's t range
@@ -382,12 +386,18 @@ extern "C" int tnp_raycaster_build(tnp_raycaster* r, const float* d_V, int64_t n
   (void)nV;
   if (r->off) { TNP_CHECK(hipFree(r->off)); r->off = nullptr; }
   if (r->items) { TNP_CHECK(hipFree(r->items)); r->items = nullptr; }
-  // ~2 triangles per cell, cubic cells over the box
-  float ext[3], mx = 0.f;
+  // ~2 triangles per cell, cubic cells over the box.  The grid is the box
+  // padded by 1e-5 of its longest side on every face, so it contains the mesh
+  // on a flat axis too (a ray is clipped to the grid: a mesh plane outside it
+  // would be searched from the wrong column of cells) and at any scale.
+  float ext[3], mx = 0.f, amax = 0.f;
   for (int d = 0; d < 3; ++d) {
-    ext[d] = std::max(bbox_hi[d] - bbox_lo[d], 1e-6f);
-    mx = std::max(mx, ext[d]);
+    mx = std::max(mx, bbox_hi[d] - bbox_lo[d]);
+    amax = std::max(amax, std::max(std::fabs(bbox_lo[d]), std::fabs(bbox_hi[d])));
   }
+  if (!(mx > 0.f)) mx = amax > 0.f ? amax : 1.f;  // a mesh of one point
+  const float pad = 1e-5f * mx;
+  for (int d = 0; d < 3; ++d) ext[d] = (bbox_hi[d] - bbox_lo[d]) + 2.f * pad;
   const double target = std::max<double>(1.0, nF / 2.0);
   const double vol = (double)ext[0] * ext[1] * ext[2];
   const float h = (float)std::cbrt(vol / target);
@@ -396,7 +406,7 @@ extern "C" int tnp_raycaster_build(tnp_raycaster* r, const float* d_V, int64_t n
   for (int d = 0; d < 3; ++d) {
     g.res[d] = (int)std::min(512.0, std::max(1.0, std::ceil((double)ext[d] / h)));
     g.cell[d] = ext[d] / g.res[d] * 1.0001f;
-    g.lo[d] = bbox_lo[d] - 1e-5f * mx;
+    g.lo[d] = bbox_lo[d] - pad;
     ncell *= g.res[d];
   }
   int32_t *cnt = nullptr, *cur = nullptr;
