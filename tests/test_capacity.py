@@ -24,7 +24,7 @@ def _growth(have, req, members, xs_n):
 
 
 def _simulate(members, xs_n, steps=60, have=0, overflow=None):
-    """The connect phase's sizing per step (engine.cpp): cap from the
+    """The connect phase's sizing per step (engine_step.cpp finish_connect): cap from the
     buffer, ensure cap * 8 bytes, an overflow grows to X (rounded to the
     regions).  Returns the buffer size after every step."""
     sizes = []
