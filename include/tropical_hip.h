@@ -399,6 +399,71 @@ int tnp_holes_export(tnp_holes* h, int32_t* d_status, int64_t* d_cycle_loop,
 int tnp_holes_caps(tnp_holes* h, int mode, const float* d_xyz, int64_t* d_cap_offsets,
                    int64_t* d_cap_indices, float* d_new_xyz, void* stream);
 
+/* Near-coincident vertices of a polygon soup welded, and the soup rewritten over the clusters'
+ * representatives (csrc/weld.hip): the first stage of the repair chain, in front of keeping components
+ * and capping holes.  Everything below is a function of the input alone: two calls give the same bits.
+ *
+ * Input.  The polygon soup of tnp_polygon_report, with the same checks, the same first-offender rule
+ * and the same message texts (prefix "weld"); V and P must be below 2^31.  tol must be finite and >= 0,
+ * mode 0 or 1 (-1 otherwise).  A used vertex with a coordinate that is not finite is refused (-1), the
+ * message naming the smallest such id; an unused vertex may hold anything.  P = 0: all-zero stats, no
+ * polygon, the identity map and the input's coordinate bits.
+ *
+ * Used vertices.  A vertex is used when its id occurs in d_indices.  Only used vertices take part: an
+ * unused vertex maps to itself, keeps its coordinate bits and never bridges two used ones.
+ *
+ * Close pairs.  With the fp32 coordinates converted to double, dx = xi - xj (dy, dz likewise) and
+ * d2 = dx dx + dy dy + dz dz, left to right, every difference, product and sum rounded exactly once
+ * (no fused multiply-add), used vertices i and j are close iff d2 <= (double)tol (double)tol.
+ * tol = 0 therefore welds bitwise-coincident positions, +0 being equal to -0.
+ *
+ * Clusters and the map.  A cluster is a class of the transitive closure of "close" (single linkage);
+ * its representative is its smallest id, and map[v] is the representative of v's class.
+ *
+ * Positions.  mode 0 (first): every member takes its representative's fp32 coordinates (their bits).
+ *  mode 1 (mean): every member of a class of m >= 2 takes the mean of the class's fp32 coordinates:
+ *  summed in double over the members in ascending id, divided by m once, rounded to fp32 once; a class
+ *  of one keeps its bits.  The sum's shape is the topology's: the used vertices in (representative, id)
+ *  order, cut into pieces at the multiples of 256 of that order and at the class boundaries; a piece
+ *  that is a whole 256-block is summed by a fixed tree, any other piece left to right; a class's pieces,
+ *  in order, by 64 strided partial sums and a fixed tree.  No float atomics.
+ *
+ * Welded polygons.  Every id is replaced by map[id].  Position i of a polygon is kept iff its mapped id
+ * differs from the mapped id of its cyclic predecessor (the last position is the first's).  A polygon
+ * with fewer than 3 kept positions is dropped.  The survivors keep their order, their kept positions
+ * theirs; source[k] is the input polygon of output polygon k.  A surviving polygon in which some id
+ * still occurs twice (never consecutively) is pinched: it is kept and counted, and the soup checks
+ * accept it.  Duplicate polygons are not removed.
+ *
+ * tnp_weld_stats: n_used; n_pairs, the close pairs i < j; n_clusters, the classes of >= 2 members;
+ * n_merged = n_used - the number of classes; max_cluster, the largest class (1 when nothing welds);
+ * n_polygons and n_indices of the output; n_dropped_polygons; n_pinched; max_shift, the largest
+ * distance from a used vertex to its output position: sqrt(d2) by the rule above in double, rounded to
+ * fp32, reduced by an integer maximum over the bit patterns.
+ *
+ * build runs the checks and keeps the result in the handle (replacing that of an earlier build); it
+ * synchronises `stream`.  h_stats may be NULL.  export copies map int64 [V], the positions fp32 [V x 3],
+ * offsets int64 [n_polygons + 1], indices int64 [n_indices] and source int64 [n_polygons]; any may be
+ * NULL.
+ *
+ * Cost.  The pairs are proposed by a uniform grid of cell size h = max(tol (1 + 2^-10), largest extent
+ * of the used vertices' box / 2^21) and decided by the predicate alone: a vertex meets the population of
+ * its own and the 26 neighbouring cells, so a tolerance near the whole extent makes the search
+ * O(n_used^2) -- correct, and slow.  The pinch test costs the sum of the squared output degrees. */
+typedef struct tnp_weld_stats {
+  int64_t n_used, n_pairs, n_clusters, n_merged, max_cluster;
+  int64_t n_polygons, n_indices, n_dropped_polygons, n_pinched;
+  float max_shift;
+} tnp_weld_stats;
+typedef struct tnp_weld tnp_weld;
+int tnp_weld_create(tnp_weld** out, int device);
+void tnp_weld_destroy(tnp_weld* w);
+int tnp_weld_build(tnp_weld* w, const float* d_xyz, int64_t V, const int64_t* d_offsets,
+                   const int64_t* d_indices, int64_t P, float tol, int mode, tnp_weld_stats* h_stats,
+                   void* stream);
+int tnp_weld_export(tnp_weld* w, int64_t* d_map, float* d_xyz_out, int64_t* d_offsets,
+                    int64_t* d_indices, int64_t* d_source, void* stream);
+
 /* 1: subpoly_(..., force=False) -- the curve-approximation branch
  * (subpoly.py:120-177, 201-207; geometry.py:24-138, 259-299;
  * subpoly_debug.py:121-165, 234-271): new vertices of non-axis-aligned split

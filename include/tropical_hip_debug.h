@@ -116,6 +116,12 @@ int tnp_debug_topology_stages(tnp_topology* t, int enable, double* ms, int n);
 #define TNP_HOLES_STAGES 7
 int tnp_debug_holes_stages(tnp_holes* h, int enable, double* ms, int n);
 
+/* Debug: stage times of tnp_weld_build (csrc/weld.hip), as tnp_debug_topology_stages: in the order
+ * check_used, grid_keys, cell_sort, search, clusters, positions, rewrite.  A build with P = 0 records
+ * none.  Returns the number of stages (TNP_WELD_STAGES), -1 on error. */
+#define TNP_WELD_STAGES 7
+int tnp_debug_weld_stages(tnp_weld* w, int enable, double* ms, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -42,7 +42,15 @@ oriented boundary loop of at most N edges of that file (of the polygon file
 without --keep-largest) with one polygon, writes the result next to it as
 ..._filled.ply and prints "Ours (holes): L loops, K capped (<= N edges), S
 non-simple, U unoriented, T longer; boundary edges B0 -> B1, closed components
-C0 -> C1" (tnp_holes_*).
+C0 -> C1" (tnp_holes_*);
+--weld TOL (TOL > 0, implies --components) first welds the polygon surface's
+vertices that lie within TOL of each other (single linkage, the cluster's
+smallest id stays), writes our_poly_mesh_{m}_{seed}_welded.ply and prints
+"Ours (weld): tol T, M of U vertices merged into C clusters (largest K, moved
+<= S), D polygons dropped, boundary edges B0 -> B1, non-manifold N0 -> N1,
+Euler E0 -> E1" (tnp_weld_*); --components, --keep-largest and --fill-holes
+then act on the welded surface, their files named ..._welded_largest{N}.ply
+and so on.
 """
 from __future__ import annotations
 
@@ -131,6 +139,9 @@ def parse_args(argv=None):
     p.add_argument("--fill-holes", default=0, type=int, metavar="N",
                    help="also cap the simple boundary loops of at most N >= 3 edges of the last mesh written and "
                         "write it as *_filled.ply (implies --components)")
+    p.add_argument("--weld", default=0.0, type=float, metavar="TOL",
+                   help="first weld the polygon surface's vertices within TOL > 0 of each other, write it as "
+                        "*_welded.ply and run --components / --keep-largest / --fill-holes on it (implies --components)")
     p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
     p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
     args = p.parse_args(argv)
@@ -138,7 +149,9 @@ def parse_args(argv=None):
         p.error("--keep-largest: N >= 0")
     if args.fill_holes < 0 or args.fill_holes in (1, 2):
         p.error("--fill-holes: N >= 3 (a loop has at least 3 edges), or 0 for none")
-    args.components = args.components or args.keep_largest > 0 or args.fill_holes > 0
+    if args.weld != 0.0 and not (args.weld > 0 and args.weld < float("inf")):
+        p.error("--weld: a finite TOL > 0 (0 for none)")
+    args.components = args.components or args.keep_largest > 0 or args.fill_holes > 0 or args.weld > 0
     args.polygons = args.polygons or args.components
     try:
         check_shape(args.layers, args.hidden)
@@ -252,6 +265,26 @@ def export_polygons(pmesh: PolygonMesh, verts, path: str):
     print(f"Ours (polygons): {r['n_polygons']} faces, mean degree {mean:.2f}, edges {r['n_edges']} "
           f"(boundary {r['e_boundary']}, non-manifold {r['e_nonmanifold']}, misoriented {r['e_misoriented']}), "
           f"euler {r['euler']}, max planarity dev {r['max_dev']:.3g}")
+
+
+def export_welded(pmesh: PolygonMesh, verts, path: str, tol: float):
+    """--weld TOL: the polygon surface (over our_mesh's scaled vertices
+    `verts`) with the vertices within `tol` of each other welded, written next
+    to `path`, the polygon file (..._welded.ply), and one line on what that
+    closed.  Returns (welded mesh, its file's path): what --components,
+    --keep-largest and --fill-holes then work on."""
+    from tropical.utils.weld import weld
+    pm = PolygonMesh(verts, pmesh.offsets, pmesh.indices, pmesh.normals)
+    welded, st = weld(pm, tol, position="first")
+    out = f"{os.path.splitext(path)[0]}_welded.ply"
+    welded.export(out)
+    r0 = polygon_report(pm.vertices, pm.offsets, pm.indices)
+    r1 = polygon_report(welded.vertices, welded.offsets, welded.indices)
+    print(f"Ours (weld): tol {tol:g}, {st['n_merged']} of {st['n_used']} vertices merged into {st['n_clusters']} "
+          f"clusters (largest {st['max_cluster']}, moved <= {st['max_shift']:.3g}), "
+          f"{st['n_dropped_polygons']} polygons dropped, boundary edges {r0['e_boundary']} -> {r1['e_boundary']}, "
+          f"non-manifold {r0['e_nonmanifold']} -> {r1['e_nonmanifold']}, Euler {r0['euler']} -> {r1['euler']}")
+    return welded, out
 
 
 def export_components(pmesh: PolygonMesh, verts, path: str, keep_largest: int = 0):
@@ -383,10 +416,14 @@ def main(argv=None):
     if args.polygons:
         export_polygons(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"))
     if args.components:
-        topo = export_components(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.keep_largest)
+        poly_path = os.path.join(out_dir, f"our_poly_mesh_{tag}.ply")
+        poly_verts = verts
+        if args.weld:
+            pmesh, poly_path = export_welded(pmesh, verts, poly_path, args.weld)
+            poly_verts = pmesh.vertices
+        topo = export_components(pmesh, poly_verts, poly_path, args.keep_largest)
         if args.fill_holes:
-            export_filled(pmesh, verts, os.path.join(out_dir, f"our_poly_mesh_{tag}.ply"), args.fill_holes, topo,
-                          args.keep_largest)
+            export_filled(pmesh, poly_verts, poly_path, args.fill_holes, topo, args.keep_largest)
     if not args.eval:
         return 0
     evaluate(net, our_mesh, our_t, out_dir, tag)
