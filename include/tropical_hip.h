@@ -464,6 +464,81 @@ int tnp_weld_build(tnp_weld* w, const float* d_xyz, int64_t V, const int64_t* d_
 int tnp_weld_export(tnp_weld* w, int64_t* d_map, float* d_xyz_out, int64_t* d_offsets,
                     int64_t* d_indices, int64_t* d_source, void* stream);
 
+/* The polygon surface simplified by vertex clustering (csrc/simplify.hip): the used vertices of a
+ * polygon soup that share a cell of a uniform grid become one vertex, the soup is rewritten over the
+ * cells' representatives and the duplicate polygons that makes are removed.  It sits in the repair
+ * chain behind tnp_weld_* and in front of keeping components and capping holes, and is the budget
+ * control of the surface: `cell` is the answer's resolution.  Everything below is a function of the
+ * input alone: two calls give the same bits.
+ *
+ * Input.  The polygon soup of tnp_polygon_report, with the same checks, the same first-offender rule
+ * and the same message texts (prefix "simplify"); V and P must be below 2^31.  cell must be finite and
+ * > 0, mode 0 or 1 (-1 otherwise).  A used vertex with a coordinate that is not finite is refused (-1),
+ * the message naming the smallest such id; an unused vertex may hold anything.  P = 0: all-zero stats,
+ * no polygon, the identity map and the input's coordinate bits.
+ *
+ * Used vertices.  As tnp_weld_*: a vertex is used when its id occurs in d_indices.  Only used vertices
+ * take part: an unused vertex maps to itself and keeps its coordinate bits.
+ *
+ * The grid.  lo is the per-axis minimum of the used vertices' fp32 coordinates, as double.  A vertex's
+ * cell coordinate on an axis is floor(((double)x - lo) / (double)cell): one rounded difference, one
+ * rounded quotient, no fused multiply-add.  An axis that needs more than 2^21 cells (the largest cell
+ * coordinate on it + 1) is refused (-1), the message naming the axis and the count: nothing is clamped,
+ * because here the cell is the answer.
+ *
+ * Classes and the map.  A class is the set of used vertices of one cell; its representative is its
+ * smallest id, and map[v] is the representative of v's class.
+ *
+ * Positions.  mode 0 (mean): every member of a class of m >= 2 takes the mean of the class's fp32
+ *  coordinates by exactly tnp_weld_*'s mode-1 rule: the used vertices in (representative, id) order, cut
+ *  into pieces at the multiples of 256 of that order and at the class boundaries, the double sums in
+ *  that fixed shape, one division by m, one rounding to fp32; a class of one keeps its bits.
+ *  mode 1 (nearest): every member takes the coordinate bits of the member whose d2 to that fp32 mean is
+ *  smallest, d2 being tnp_weld_*'s predicate arithmetic in double; ties go to the smallest id.  The
+ *  output positions are then a subset of the input's.  No float atomics: the minimum is taken by integer
+ *  atomics over the bit pattern of d2, then over the ids that reach it.
+ *
+ * Rewritten polygons.  tnp_weld_*'s rule, unchanged: every id is replaced by map[id]; a position is
+ * kept iff its mapped id differs from that of its cyclic predecessor; a polygon with fewer than 3 kept
+ * positions is dropped (n_dropped_polygons); a survivor in which an id still occurs twice is pinched.
+ *
+ * Duplicates.  A survivor's canonical form is the lexicographically smallest rotation of its id
+ * sequence (pinched polygons included).  A survivor whose canonical form equals that of an earlier
+ * survivor is a duplicate: it is removed and counted in n_duplicate_polygons.  A survivor that is not
+ * a duplicate and whose reversed sequence has the canonical form of an earlier survivor is folded: it is
+ * kept and counted in n_folded.  The comparison is exact, id by id; a 64-bit hash of the canonical form
+ * only buckets the polygons, and no result depends on it.  The polygons that remain keep their order
+ * and their ids as rewritten (not rotated); source[k] is the input polygon of output polygon k.
+ *
+ * tnp_simplify_stats: n_used; n_cells, the occupied cells = the classes; max_cell, the largest class;
+ * n_polygons and n_indices of the output; n_dropped_polygons; n_duplicate_polygons; n_folded;
+ * n_pinched, the pinched polygons of the output; max_shift as tnp_weld_*'s -- at most sqrt(3) cell
+ * plus rounding, every member and the mean lying in one cell.
+ *
+ * build runs the checks and keeps the result in the handle (replacing that of an earlier build); it
+ * synchronises `stream`.  h_stats may be NULL.  export copies map int64 [V], the positions fp32 [V x 3],
+ * offsets int64 [n_polygons + 1], indices int64 [n_indices] and source int64 [n_polygons]; any may be
+ * NULL.
+ *
+ * Cost.  One sort of the used vertices by cell key, one by (representative, id) when a class has two
+ * members, one of the survivors by hash.  The canonical form costs a polygon its degree times the
+ * occurrences of its smallest id; the duplicate search costs the sum over the runs of equal hash of the
+ * squared run length times the degree -- a soup of n copies of one polygon is O(n^2), correct and slow.
+ * The pinch test costs the sum of the squared degrees after the rewrite. */
+typedef struct tnp_simplify_stats {
+  int64_t n_used, n_cells, max_cell;
+  int64_t n_polygons, n_indices, n_dropped_polygons, n_duplicate_polygons, n_folded, n_pinched;
+  float max_shift;
+} tnp_simplify_stats;
+typedef struct tnp_simplify tnp_simplify;
+int tnp_simplify_create(tnp_simplify** out, int device);
+void tnp_simplify_destroy(tnp_simplify* h);
+int tnp_simplify_build(tnp_simplify* h, const float* d_xyz, int64_t V, const int64_t* d_offsets,
+                       const int64_t* d_indices, int64_t P, float cell, int mode,
+                       tnp_simplify_stats* h_stats, void* stream);
+int tnp_simplify_export(tnp_simplify* h, int64_t* d_map, float* d_xyz_out, int64_t* d_offsets,
+                        int64_t* d_indices, int64_t* d_source, void* stream);
+
 /* 1: subpoly_(..., force=False) -- the curve-approximation branch
  * (subpoly.py:120-177, 201-207; geometry.py:24-138, 259-299;
  * subpoly_debug.py:121-165, 234-271): new vertices of non-axis-aligned split

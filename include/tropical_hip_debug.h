@@ -122,6 +122,12 @@ int tnp_debug_holes_stages(tnp_holes* h, int enable, double* ms, int n);
 #define TNP_WELD_STAGES 7
 int tnp_debug_weld_stages(tnp_weld* w, int enable, double* ms, int n);
 
+/* Debug: stage times of tnp_simplify_build (csrc/simplify.hip), as tnp_debug_topology_stages: in the
+ * order check_used, grid_keys, cell_sort, classes, positions, rewrite, duplicates.  A build with
+ * P = 0 records none.  Returns the number of stages (TNP_SIMPLIFY_STAGES), -1 on error. */
+#define TNP_SIMPLIFY_STAGES 7
+int tnp_debug_simplify_stages(tnp_simplify* h, int enable, double* ms, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2,8 +2,8 @@
 // [P + 1], d_indices int64) makes on the device before anything is read
 // through an id, and the edge keys three of them build in the same pass --
 // tnp_polygon_report (polygons.hip), tnp_render_raster (render.hip),
-// tnp_topology_build (topology.hip), tnp_holes_build (holes.hip) and
-// tnp_weld_build (weld.hip) share them, so all refuse the same input and name the same first offender.  The
+// tnp_topology_build (topology.hip), tnp_holes_build (holes.hip),
+// tnp_weld_build (weld.hip) and tnp_simplify_build (simplify.hip) share them, so all refuse the same input and name the same first offender.  The
 // host side around these kernels is soup_host.h's.
 //
 // ctr[SOUP_ERR]: the error word, (position << 3) | code under atomicMin, so

@@ -1,11 +1,11 @@
 // The host side every entry point that takes a polygon soup shares --
 // tnp_polygon_report (polygons.hip), tnp_render_raster (render.hip),
 // tnp_topology_build (topology.hip), tnp_holes_build (holes.hip),
-// tnp_weld_build (weld.hip): the argument refusals, the per-call scratch, the two halves of the check front around
+// tnp_weld_build (weld.hip), tnp_simplify_build (simplify.hip): the argument refusals, the per-call scratch, the two halves of the check front around
 // soup_check.h's kernels, the stand-alone scan, the stage events and the
 // handle boilerplate.  A new consumer starts from soup_args, soup_offsets and
-// soup_verdict and follows no id before the verdict.  Included by those five
-// files only, the last three through topo_common.h (anonymous namespace).
+// soup_verdict and follows no id before the verdict.  Included by those six
+// files only, the last four through topo_common.h (anonymous namespace).
 #pragma once
 #include <vector>
 
@@ -166,7 +166,7 @@ struct Stages {
   }
 };
 
-// ---- the handles (tnp_topology, tnp_holes, tnp_weld): H has device, timed, n_ms and
+// ---- the handles (tnp_topology, tnp_holes, tnp_weld, tnp_simplify): H has device, timed, n_ms and
 // ms[N]; drop(h) frees what the last build left ----
 template <class H>
 int handle_create(const char* who, H** out, int device) {

@@ -1,8 +1,8 @@
 // What tnp_topology_build (topology.hip), tnp_holes_build (holes.hip) and
-// tnp_weld_build (weld.hip) share beyond soup_host.h: the lock-free union-find,
+// tnp_weld_build (weld.hip; tnp_simplify_build through weld_common.h) share beyond soup_host.h: the lock-free union-find,
 // the per-class wave reductions, the boundary graph's classes (one union per
 // edge used once, the root flags and their scan) and the segmented double
-// sums.  Included by those three files only (anonymous namespace).
+// sums.  Included by those files only (anonymous namespace).
 #pragma once
 #include "kernels.h"
 #include "soup_host.h"

@@ -1,9 +1,10 @@
 // tnp_weld_*: the near-coincident vertices of a polygon soup welded by single
 // linkage, and the soup rewritten over the clusters' representatives
 // (include/tropical_hip.h has the definitions).  The front is soup_host.h's,
-// the union-find and the segmented double sums are topo_common.h's;
-// tnp_weld_build is its stages in order, one function each, with the state in
-// a WeldBuild.
+// the union-find and the segmented double sums are topo_common.h's, the used
+// vertices, the class means, the drift and the rewrite are weld_common.h's
+// (tnp_simplify_build shares them); tnp_weld_build is its stages in order, one
+// function each, with the state in a WeldBuild.
 //
 //   k_soup_offsets, k_weld_ids   the soup's checks; used[v] = 1 per valid id
 //   k_weld_box, scan             per used vertex: the finite check (the smallest
@@ -38,7 +39,7 @@
 
 #include "../../include/tropical_hip_debug.h"
 #include "kernels.h"
-#include "topo_common.h"
+#include "weld_common.h"
 
 struct tnp_weld {
   int device = 0;
@@ -57,85 +58,15 @@ struct tnp_weld {
 namespace {
 
 // the counters of a build (int64 words, a block of their own behind the
-// front's two): WC_BAD, WC_LO* start at all ones, the others at zero
+// front's two): WC_BAD, WC_LO* start at all ones, the others at zero;
+// WC_SHIFT .. WC_PINCHED are weld_common.h's RW_* words
 enum { WC_BAD, WC_LOX, WC_LOY, WC_LOZ, WC_HIX, WC_HIY, WC_HIZ, WC_NUSED, WC_PAIRS, WC_CLASSES, WC_CLUSTERS,
        WC_LARGEST, WC_SHIFT, WC_KEPT, WC_NPOLY, WC_NIDX, WC_PINCHED, WC_NSEG, WC_N };
+static_assert(WC_KEPT == WC_SHIFT + RW_KEPT && WC_NPOLY == WC_SHIFT + RW_NPOLY && WC_NIDX == WC_SHIFT + RW_NIDX &&
+              WC_PINCHED == WC_SHIFT + RW_PINCHED, "counter layout");
 
 constexpr int CELL_BITS = 21;          // three cell coordinates fill 63 key bits
 constexpr double CELL_SLACK = 0x1p-10;  // h >= tol (1 + slack): DESIGN 7h
-
-// fp32 <-> uint32 keeping the order (-0 below +0, which no caller tells apart)
-__device__ __forceinline__ uint32_t f2ord(float f) {
-  const uint32_t u = __float_as_uint(f);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-inline float ord2f(uint32_t o) {
-  const uint32_t u = (o & 0x80000000u) ? (o & 0x7fffffffu) : ~o;
-  float f;
-  memcpy(&f, &u, sizeof f);
-  return f;
-}
-
-__device__ __forceinline__ void count_lanes(bool f, int64_t* word) {
-  const uint64_t m = __ballot(f);
-  if (tnp::lane() == 0 && m) atomicAdd(reinterpret_cast<unsigned long long*>(word), (unsigned long long)__popcll(m));
-}
-
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long y = __shfl_xor(v, o, 64);
-    v = y > v ? y : v;
-  }
-  return v;
-}
-
-// the squared distance of the definitions: fp32 -> double, every product and
-// sum rounded once, left to right
-__device__ __forceinline__ double dist2(const float* __restrict__ a, const float* __restrict__ b) {
-  const double dx = __dsub_rn((double)a[0], (double)b[0]);
-  const double dy = __dsub_rn((double)a[1], (double)b[1]);
-  const double dz = __dsub_rn((double)a[2], (double)b[2]);
-  return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_ids(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n, int64_t V,
-           int64_t* __restrict__ ctr, int32_t* __restrict__ used) {
-  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (i >= n) return;
-  int64_t a, b;
-  bool b_ok;
-  if (soup_check_id(off, P, idx, i, V, ctr, a, b, b_ok)) used[a] = 1;
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_box(const float* __restrict__ xyz, const int32_t* __restrict__ used, int64_t V, int64_t* __restrict__ wc) {
-  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  const bool on = v < V && used[v];
-  unsigned long long lo[3] = {~0ull, ~0ull, ~0ull}, hi[3] = {0ull, 0ull, 0ull}, bad = ~0ull;
-  if (on) {
-    const float* p = xyz + 3 * v;
-    if (isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2])) {
-#pragma unroll
-      for (int q = 0; q < 3; ++q) lo[q] = hi[q] = f2ord(p[q]);
-    } else {
-      bad = (unsigned long long)v;
-    }
-  }
-  if (!__ballot(on)) return;  // (a whole wave)
-  unsigned long long* w = reinterpret_cast<unsigned long long*>(wc);
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const unsigned long long h = wave_max_u64(hi[q]), l = ~wave_max_u64(~lo[q]);
-    if (tnp::lane() == 0 && l <= h) {
-      atomicMin(w + WC_LOX + q, l);
-      atomicMax(w + WC_HIX + q, h);
-    }
-  }
-  bad = ~wave_max_u64(~bad);
-  if (tnp::lane() == 0 && bad != ~0ull) atomicMin(w + WC_BAD, bad);
-}
 
 struct Grid {
   double lo[3], h;
@@ -233,144 +164,6 @@ k_weld_roots(const int32_t* __restrict__ root, const int32_t* __restrict__ used,
   if (tnp::lane() == 0 && mx) atomicMax(reinterpret_cast<unsigned long long*>(wc + WC_LARGEST), mx);
 }
 
-// mode 0; an unused vertex is its own representative
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_first(const float* __restrict__ xyz, const int32_t* __restrict__ root, int64_t V, float* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (v >= V) return;
-  const float* p = xyz + 3 * (int64_t)root[v];
-#pragma unroll
-  for (int q = 0; q < 3; ++q) out[3 * v + q] = p[q];
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_mkeys(const int32_t* __restrict__ used, const int64_t* __restrict__ urank, const int32_t* __restrict__ root,
-             int64_t V, int64_t U, int shift, uint64_t* __restrict__ keys) {
-  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (v >= V || !used[v]) return;
-  const int64_t j = urank[v];
-  if (j < U) keys[j] = ((uint64_t)root[v] << shift) | (uint64_t)v;
-}
-
-// sorted (representative, id) keys: a class starts at its representative
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_heads(const uint64_t* __restrict__ sk, int64_t U, int shift, int32_t* __restrict__ head) {
-  const int64_t j = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (j < U) head[j] = (sk[j] >> shift) == (sk[j] & (((uint64_t)1 << shift) - 1));
-}
-
-// start[c] of class c (in ascending representative), seg[representative] = c;
-// thread 0 closes the starts
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_starts(const uint64_t* __restrict__ sk, const int32_t* __restrict__ head, const int64_t* __restrict__ hrank,
-              int64_t U, int64_t nseg, int shift, int64_t* __restrict__ start, int32_t* __restrict__ seg) {
-  const int64_t j = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (j == 0) start[nseg] = U;
-  if (j >= U || !head[j]) return;
-  const int64_t c = hrank[j];
-  if (c >= nseg) return;
-  start[c] = j;
-  seg[sk[j] >> shift] = (int32_t)c;
-}
-
-struct VertXYZ {  // the coordinates of vertex v
-  const float* xyz;
-  __device__ __forceinline__ void operator()(uint64_t v, double* out) const {
-    const float* q = xyz + 3 * v;
-    out[0] = (double)q[0], out[1] = (double)q[1], out[2] = (double)q[2];
-  }
-};
-
-// mode 1; a class of one (an unused vertex too) keeps its bits
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_mean(const float* __restrict__ xyz, const int32_t* __restrict__ used, const int32_t* __restrict__ root,
-            const int* __restrict__ csize, const int32_t* __restrict__ seg, const double* __restrict__ sums,
-            int64_t nseg, int64_t V, float* __restrict__ out) {
-  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (v >= V) return;
-  const int r = root[v];
-  const int m = used[v] ? csize[r] : 1;
-  const int64_t c = m >= 2 ? seg[r] : 0;
-#pragma unroll
-  for (int q = 0; q < 3; ++q)
-    out[3 * v + q] = (m >= 2 && c < nseg) ? (float)(sums[(int64_t)q * nseg + c] / (double)m) : xyz[3 * v + q];
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_shift(const float* __restrict__ xyz, const float* __restrict__ out, const int32_t* __restrict__ used, int64_t V,
-             int64_t* __restrict__ wc) {
-  const int64_t v = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  unsigned long long b = 0;
-  if (v < V && used[v]) b = __float_as_uint((float)__dsqrt_rn(dist2(xyz + 3 * v, out + 3 * v)));
-  b = wave_max_u64(b);
-  if (tnp::lane() == 0 && b) atomicMax(reinterpret_cast<unsigned long long*>(wc + WC_SHIFT), b);
-}
-
-// keep[i]: the mapped id at i differs from its cyclic predecessor's; keep[n] = 0
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_keep(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n,
-            const int32_t* __restrict__ root, int32_t* __restrict__ keep) {
-  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (i > n) return;
-  if (i == n) { keep[n] = 0; return; }
-  const int64_t p = soup_polygon_of(off, P, i);
-  const int64_t j = i == off[p] ? off[p + 1] - 1 : i - 1;
-  keep[i] = root[idx[i]] != root[idx[j]];
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_degrees(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ krank,
-               int32_t* __restrict__ pkeep, int32_t* __restrict__ pdeg) {
-  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (p >= P) return;
-  const int64_t d = krank[off[p + 1]] - krank[off[p]];
-  pkeep[p] = d >= 3;
-  pdeg[p] = d >= 3 ? (int32_t)d : 0;
-}
-
-// thread 0 closes the offsets (no survivor included)
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_rows(int64_t P, const int32_t* __restrict__ pkeep, const int64_t* __restrict__ prank,
-            const int64_t* __restrict__ poff, int64_t P2, int64_t N2, int64_t* __restrict__ out_off,
-            int64_t* __restrict__ source) {
-  const int64_t p = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (p == 0) out_off[P2] = N2;
-  if (p >= P || !pkeep[p]) return;
-  const int64_t k = prank[p];
-  if (k >= P2) return;
-  out_off[k] = poff[p];
-  source[k] = p;
-}
-
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_scatter(const int64_t* __restrict__ off, int64_t P, const int64_t* __restrict__ idx, int64_t n,
-               const int32_t* __restrict__ root, const int32_t* __restrict__ keep, const int64_t* __restrict__ krank,
-               const int32_t* __restrict__ pkeep, const int64_t* __restrict__ poff, int64_t N2,
-               int64_t* __restrict__ out_idx) {
-  const int64_t i = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  if (i >= n || !keep[i]) return;
-  const int64_t p = soup_polygon_of(off, P, i);
-  if (!pkeep[p]) return;
-  const int64_t at = poff[p] + (krank[i] - krank[off[p]]);
-  if (at < N2) out_idx[at] = root[idx[i]];
-}
-
-// an output polygon is pinched when an id occurs twice in it: position t looks
-// for its id further on, and the first finder of a polygon counts it
-__global__ void __launch_bounds__(TNP_BLOCK)
-k_weld_pinched(const int64_t* __restrict__ out_off, int64_t P2, const int64_t* __restrict__ out_idx, int64_t N2,
-               int* __restrict__ pinched, int64_t* __restrict__ wc) {
-  const int64_t t = (int64_t)blockIdx.x * TNP_BLOCK + threadIdx.x;
-  bool first = false;
-  if (t < N2) {
-    const int64_t p = soup_polygon_of(out_off, P2, t), e = out_off[p + 1], a = out_idx[t];
-    bool dup = false;
-    for (int64_t u = t + 1; u < e && !dup; ++u) dup = out_idx[u] == a;
-    first = dup && atomicExch(pinched + p, 1) == 0;
-  }
-  count_lanes(first, wc + WC_PINCHED);
-}
-
 void drop_weld(tnp_weld* h) {
   void* all[] = {h->map, h->xyz, h->offsets, h->indices, h->source};
   for (void* p : all)
@@ -397,7 +190,7 @@ struct WeldBuild {
   int64_t c[WC_N] = {};  // the counters as last read back
   int64_t n = 0, U = 0;
   Grid g = {};
-  int32_t *used = nullptr, *root = nullptr, *ids = nullptr, *seg = nullptr;
+  int32_t *used = nullptr, *root = nullptr, *ids = nullptr;
   int64_t* urank = nullptr;
   uint64_t* keys = nullptr;
   int *parent = nullptr, *csize = nullptr;
@@ -437,7 +230,7 @@ int WeldBuild::used_box() {
   SOUP_LAUNCH(k_weld_ids, n, off, P, idx, n, V, ctr, used);
   int64_t front[1];
   if (soup_verdict("weld", off, idx, V, ctr, front, 1, s)) return -1;
-  SOUP_LAUNCH(k_weld_box, V, xyz, used, V, wc);
+  SOUP_LAUNCH(k_weld_box, V, xyz, used, V, wc + WC_LOX, wc + WC_HIX, wc + WC_BAD);
   if (scan_flags(scr, used, V, urank, wc + WC_NUSED, s)) return -1;
   if (read_counters()) return -1;
   st.mark();
@@ -515,90 +308,25 @@ int WeldBuild::positions() {
   if (mode == 0 || ws.n_clusters == 0) {
     SOUP_LAUNCH(k_weld_first, V, xyz, root, V, h->xyz);
   } else {
-    const int shift = bits_for(V), key_bits = 2 * shift;
-    const int64_t nseg = c[WC_CLASSES];
-    const size_t sort_bytes = sort_scratch_bytes(U, key_bits);
-    {
-      const size_t need = 2 * Scratch::pad(U * sizeof(uint64_t)) + Scratch::pad(sort_bytes) +
-                          Scratch::pad(U * sizeof(int32_t)) + Scratch::pad(U * sizeof(int64_t)) +
-                          Scratch::pad(((size_t)scan_tiles(U) + 1) * sizeof(uint64_t)) +
-                          Scratch::pad((nseg + 1) * sizeof(int64_t)) + Scratch::pad(V * sizeof(int32_t)) +
-                          Scratch::pad(3 * U * sizeof(double)) + Scratch::pad(3 * nseg * sizeof(double));
-      if (!scr.reserve(need)) return -1;
-    }
-    uint64_t* ka = scr.arr<uint64_t>(U);
-    uint64_t* kb = scr.arr<uint64_t>(U);
-    void* sort_scr = scr.get(sort_bytes);
-    int32_t* head = scr.arr<int32_t>(U);
-    int64_t* hrank = scr.arr<int64_t>(U);
-    int64_t* start = scr.arr<int64_t>(nseg + 1);
-    seg = scr.arr<int32_t>(V);
-    double* pieces = scr.arr<double>(3 * U);
-    double* sums = scr.arr<double>(3 * nseg);
-    if (!ka || !kb || !sort_scr || !head || !hrank || !start || !seg || !pieces || !sums) return -1;
-    uint64_t* sk = nullptr;
-    SOUP_LAUNCH(k_weld_mkeys, V, used, urank, root, V, U, shift, ka);
-    if (sort_keys_u64(ka, kb, U, key_bits, sort_scr, sort_bytes, &sk, s)) return -1;
-    SOUP_LAUNCH(k_weld_heads, U, sk, U, shift, head);
-    if (scan_flags(scr, head, U, hrank, wc + WC_NSEG, s)) return -1;
-    // (a start the heads do not reach stays inside the pieces)
-    TNP_CHECK(hipMemsetAsync(start, 0, (size_t)(nseg + 1) * sizeof(int64_t), s));
-    SOUP_LAUNCH(k_weld_starts, U, sk, head, hrank, U, nseg, shift, start, seg);
-    hipLaunchKernelGGL((k_seg_pieces<3, VertXYZ>), dim3(tnp_grid(U, SEG)), dim3(TNP_BLOCK), 0, s, sk, U, shift,
-                       VertXYZ{xyz}, pieces);
-    hipLaunchKernelGGL(k_seg_final<3>, dim3(tnp_grid(nseg, TNP_WAVES)), dim3(TNP_BLOCK), 0, s, start, nseg, U, pieces,
-                       sums);
-    TNP_CHECK(hipGetLastError());
-    SOUP_LAUNCH(k_weld_mean, V, xyz, used, root, csize, seg, sums, nseg, V, h->xyz);
+    if (class_means(scr, xyz, used, urank, root, csize, V, U, c[WC_CLASSES], wc + WC_NSEG, h->xyz, s)) return -1;
   }
-  SOUP_LAUNCH(k_weld_shift, V, xyz, h->xyz, used, V, wc);
+  SOUP_LAUNCH(k_weld_shift, V, xyz, h->xyz, used, V, wc + WC_SHIFT);
   st.mark();
   return 0;
 }
 
 // stage rewrite: the keep flags, the new degrees, the survivors and the output soup
 int WeldBuild::rewrite() {
-  {
-    const size_t need = Scratch::pad((n + 1) * sizeof(int32_t)) + Scratch::pad((n + 1) * sizeof(int64_t)) +
-                        2 * Scratch::pad(P * sizeof(int32_t)) + 2 * Scratch::pad(P * sizeof(int64_t)) +
-                        Scratch::pad(((size_t)scan_tiles(n + 1) + 1) * sizeof(uint64_t)) +
-                        2 * Scratch::pad(((size_t)scan_tiles(P) + 1) * sizeof(uint64_t));
-    if (!scr.reserve(need)) return -1;
-  }
-  int32_t* keep = scr.arr<int32_t>(n + 1);
-  int64_t* krank = scr.arr<int64_t>(n + 1);
-  int32_t* pkeep = scr.arr<int32_t>(P);
-  int32_t* pdeg = scr.arr<int32_t>(P);
-  int64_t* prank = scr.arr<int64_t>(P);
-  int64_t* poff = scr.arr<int64_t>(P);
-  if (!keep || !krank || !pkeep || !pdeg || !prank || !poff) return -1;
-  SOUP_LAUNCH(k_weld_keep, n + 1, off, P, idx, n, root, keep);
-  if (scan_flags(scr, keep, n + 1, krank, wc + WC_KEPT, s)) return -1;
-  SOUP_LAUNCH(k_weld_degrees, P, off, P, krank, pkeep, pdeg);
-  if (scan_flags(scr, pkeep, P, prank, wc + WC_NPOLY, s)) return -1;
-  if (scan_flags(scr, pdeg, P, poff, wc + WC_NIDX, s)) return -1;
-  if (read_counters()) return -1;
+  if (!scr.reserve(Rewrite::bytes(n, P))) return -1;
+  Rewrite rw{off, idx, n, P, root, wc + WC_SHIFT};
+  if (rw.count(scr, s) || read_counters() || rw.sane("weld", c + WC_SHIFT)) return -1;
   const int64_t P2 = c[WC_NPOLY], N2 = c[WC_NIDX];
-  if (P2 < 0 || P2 > P || N2 < 3 * P2 || N2 > c[WC_KEPT] || c[WC_KEPT] > n) {
-    tnp_set_error("weld: %lld polygons of %lld kept with %lld ids of %lld", (long long)P2, (long long)P,
-                  (long long)N2, (long long)n);
-    return -1;
-  }
   TNP_CHECK(hipMalloc(&h->offsets, (size_t)(P2 + 1) * sizeof(int64_t)));
   if (P2 > 0) {
     TNP_CHECK(hipMalloc(&h->indices, (size_t)N2 * sizeof(int64_t)));
     TNP_CHECK(hipMalloc(&h->source, (size_t)P2 * sizeof(int64_t)));
   }
-  SOUP_LAUNCH(k_weld_rows, P, P, pkeep, prank, poff, P2, N2, h->offsets, h->source);
-  if (P2 > 0) {
-    int* pinched = scr.arr<int>(P2);
-    if (!pinched) return -1;
-    TNP_CHECK(hipMemsetAsync(pinched, 0, (size_t)P2 * sizeof(int), s));
-    // (a position the scatter does not reach stays a valid id)
-    TNP_CHECK(hipMemsetAsync(h->indices, 0, (size_t)N2 * sizeof(int64_t), s));
-    SOUP_LAUNCH(k_weld_scatter, n, off, P, idx, n, root, keep, krank, pkeep, poff, N2, h->indices);
-    SOUP_LAUNCH(k_weld_pinched, N2, h->offsets, P2, h->indices, N2, pinched, wc);
-  }
+  if (rw.fill(scr, P2, N2, h->offsets, h->indices, h->source, s)) return -1;
   if (read_counters()) return -1;
   st.mark();
   ws.n_polygons = P2, ws.n_indices = N2, ws.n_dropped_polygons = P - P2, ws.n_pinched = c[WC_PINCHED];

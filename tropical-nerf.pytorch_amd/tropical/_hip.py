@@ -73,6 +73,15 @@ class TnpWeldStats(C.Structure):
         return {k: (float if k == "max_shift" else int)(getattr(self, k)) for k, _ in self._fields_}
 
 
+class TnpSimplifyStats(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_used", "n_cells", "max_cell", "n_polygons", "n_indices",
+                                         "n_dropped_polygons", "n_duplicate_polygons", "n_folded",
+                                         "n_pinched")] + [("max_shift", C.c_float)]
+
+    def as_dict(self):
+        return {k: (float if k == "max_shift" else int)(getattr(self, k)) for k, _ in self._fields_}
+
+
 class TnpRenderView(C.Structure):
     _fields_ = [
         ("right", C.c_float * 3), ("up", C.c_float * 3), ("toward", C.c_float * 3), ("center", C.c_float * 3),
@@ -152,6 +161,11 @@ SIGNATURES = {
     "tnp_weld_build": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _F, C.c_int, C.POINTER(TnpWeldStats), _VP]),
     "tnp_weld_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "tnp_debug_weld_stages": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.c_int]),
+    "tnp_simplify_create": (C.c_int, [C.POINTER(_VP), C.c_int]),
+    "tnp_simplify_destroy": (None, [_VP]),
+    "tnp_simplify_build": (C.c_int, [_VP, _VP, _I64, _VP, _VP, _I64, _F, C.c_int, C.POINTER(TnpSimplifyStats), _VP]),
+    "tnp_simplify_export": (C.c_int, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "tnp_debug_simplify_stages": (C.c_int, [_VP, C.c_int, C.POINTER(C.c_double), C.c_int]),
     "tnp_render_raster": (C.c_int, [_VP, _I64, _VP, _VP, _I64, C.POINTER(TnpRenderView), _I32, _VP, _VP, _VP, _VP,
                                     C.POINTER(TnpRenderStats), _VP]),
     "tnp_render_shade": (C.c_int, [_VP, _VP, _I32, _I32, _VP, _I64, _F, _F, _VP, C.POINTER(C.c_uint8), _I32, _VP,

@@ -45,10 +45,11 @@ def mesh_path(name: str) -> str:
 
 
 class StanfordDataset(torch.utils.data.Dataset):
-    def __init__(self, name: str = "dragon", mesh=None, device=None):
+    def __init__(self, name: str = "dragon", mesh=None, device=None, mesh_cell=None):
         self.R = .8
         self.name = name
         self.device = torch.device(device) if device is not None else torch.device("cuda")
+        self.mesh_cell = mesh_cell
         self.init(mesh)
         self.resample()
 
@@ -80,8 +81,20 @@ class StanfordDataset(torch.utils.data.Dataset):
             scale = (vertices.max(dim=0)[0] - vertices.min(dim=0)[0]).max()
             vertices = vertices / scale * 2
             vertices -= (vertices.max(dim=0)[0] + vertices.min(dim=0)[0]) / 2
+        faces = np.asarray(m.faces, dtype=np.int64)
+        if self.mesh_cell is not None:
+            # clustering decimation of the (normalised) mesh, as the reference's lucy scan was prepared
+            # (dataset.py:60-63): the vertices of a cell of this size become its vertex nearest to their mean
+            from ..utils.simplify import cluster_triangles
+            v, faces, st = cluster_triangles(vertices.numpy(), faces, self.mesh_cell)
+            print(f"Mesh clustered: cell {self.mesh_cell:g}, triangles {len(m.faces)} -> {len(faces)} "
+                  f"({st['n_dropped_polygons']} dropped, {st['n_duplicate_polygons']} duplicate), "
+                  f"vertices {st['n_used']} -> {st['n_cells']}", flush=True)
+            if len(faces) == 0:
+                raise ValueError(f"mesh_cell = {self.mesh_cell:g} leaves no triangle")
+            vertices = torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32))
         self.vertices = vertices
-        self.faces = torch.as_tensor(np.asarray(m.faces, dtype=np.int64))
+        self.faces = torch.as_tensor(faces)
         self.V = vertices.to(self.device)
         self.F = self.faces.to(self.device, torch.int32)
         print("BVH initialized.", flush=True)

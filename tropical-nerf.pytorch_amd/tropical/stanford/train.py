@@ -50,7 +50,19 @@ smallest id stays), writes our_poly_mesh_{m}_{seed}_welded.ply and prints
 <= S), D polygons dropped, boundary edges B0 -> B1, non-manifold N0 -> N1,
 Euler E0 -> E1" (tnp_weld_*); --components, --keep-largest and --fill-holes
 then act on the welded surface, their files named ..._welded_largest{N}.ply
-and so on.
+and so on;
+--simplify CELL (CELL > 0, implies --components; behind --weld, in front of
+--keep-largest and --fill-holes) clusters the polygon surface's vertices by the
+cells of a grid of size CELL (--simplify-position mean | nearest: the cell's
+mean, or its vertex nearest to the mean), removes the duplicate polygons that
+makes, writes ..._simplified.ply (..._welded_simplified.ply behind --weld) and
+prints "Ours (simplify): cell C (mean), U vertices -> K cells (largest M),
+polygons P0 -> P1 (D dropped, X duplicate, F folded, Q pinched), moved <= S,
+boundary edges B0 -> B1, non-manifold N0 -> N1, misoriented M0 -> M1, Euler
+E0 -> E1" (tnp_simplify_*);
+--mesh-cell CELL (with --mesh) clusters the normalised training mesh the same
+way (nearest, duplicates removed) before the signed-distance kernel and the
+sampling see it, and prints the triangle count before and after.
 """
 from __future__ import annotations
 
@@ -112,6 +124,15 @@ def shape_suffix(num_layers: int = 3, num_hidden: int = 16) -> str:
     return "" if (num_layers, num_hidden) == (3, 16) else f"_l{num_layers}h{num_hidden}"
 
 
+def _cell(text: str) -> float:
+    """argparse type of --simplify / --mesh-cell: a finite float > 0, as fp32 too (argparse names the flag)."""
+    from tropical.utils.simplify import check_cell
+    try:
+        return check_cell(float(text))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a finite CELL > 0, not {text!r}")
+
+
 def parse_args(argv=None):
     p = argparse.ArgumentParser(prog="python -m tropical.stanford.train",
                                 description="Polyhedral complex derivation from piecewise trilinear networks")
@@ -142,6 +163,14 @@ def parse_args(argv=None):
     p.add_argument("--weld", default=0.0, type=float, metavar="TOL",
                    help="first weld the polygon surface's vertices within TOL > 0 of each other, write it as "
                         "*_welded.ply and run --components / --keep-largest / --fill-holes on it (implies --components)")
+    p.add_argument("--simplify", default=None, type=_cell, metavar="CELL",
+                   help="cluster the polygon surface's vertices by the cells of a grid of size CELL > 0 (behind --weld), "
+                        "remove the duplicate polygons, write it as *_simplified.ply and run --components / "
+                        "--keep-largest / --fill-holes on it (implies --components)")
+    p.add_argument("--simplify-position", default="mean", choices=["mean", "nearest"],
+                   help="--simplify: a cell's vertex is the mean of its vertices, or the one nearest to that mean")
+    p.add_argument("--mesh-cell", default=None, type=_cell, metavar="CELL",
+                   help="cluster the (normalised) --mesh by cells of size CELL > 0 before training on it")
     p.add_argument("--layers", default=3, type=int, help="linear layers of the net (the reference: 3)")
     p.add_argument("--hidden", default=16, type=int, help="hidden units per layer (the reference: 16)")
     args = p.parse_args(argv)
@@ -151,7 +180,10 @@ def parse_args(argv=None):
         p.error("--fill-holes: N >= 3 (a loop has at least 3 edges), or 0 for none")
     if args.weld != 0.0 and not (args.weld > 0 and args.weld < float("inf")):
         p.error("--weld: a finite TOL > 0 (0 for none)")
-    args.components = args.components or args.keep_largest > 0 or args.fill_holes > 0 or args.weld > 0
+    if args.mesh_cell is not None and args.mesh is None:
+        p.error("--mesh-cell: needs --mesh")
+    args.components = (args.components or args.keep_largest > 0 or args.fill_holes > 0 or args.weld > 0
+                       or args.simplify is not None)
     args.polygons = args.polygons or args.components
     try:
         check_shape(args.layers, args.hidden)
@@ -287,6 +319,28 @@ def export_welded(pmesh: PolygonMesh, verts, path: str, tol: float):
     return welded, out
 
 
+def export_simplified(pmesh: PolygonMesh, verts, path: str, cell: float, position: str = "mean"):
+    """--simplify CELL: the polygon surface (over the vertices `verts`)
+    clustered by cells of size `cell`, written next to `path` (..._simplified.ply),
+    and one line on what that did.  Returns (simplified mesh, its file's path):
+    what --components, --keep-largest and --fill-holes then work on."""
+    from tropical.utils.simplify import simplify
+    pm = PolygonMesh(verts, pmesh.offsets, pmesh.indices, pmesh.normals)
+    out_pm, st = simplify(pm, cell, position=position)
+    out = f"{os.path.splitext(path)[0]}_simplified.ply"
+    out_pm.export(out)
+    r0 = polygon_report(pm.vertices, pm.offsets, pm.indices)
+    r1 = polygon_report(out_pm.vertices, out_pm.offsets, out_pm.indices)
+    print(f"Ours (simplify): cell {cell:g} ({position}), {st['n_used']} vertices -> {st['n_cells']} cells "
+          f"(largest {st['max_cell']}), polygons {r0['n_polygons']} -> {st['n_polygons']} "
+          f"({st['n_dropped_polygons']} dropped, {st['n_duplicate_polygons']} duplicate, {st['n_folded']} folded, "
+          f"{st['n_pinched']} pinched), moved <= {st['max_shift']:.3g}, "
+          f"boundary edges {r0['e_boundary']} -> {r1['e_boundary']}, "
+          f"non-manifold {r0['e_nonmanifold']} -> {r1['e_nonmanifold']}, "
+          f"misoriented {r0['e_misoriented']} -> {r1['e_misoriented']}, Euler {r0['euler']} -> {r1['euler']}")
+    return out_pm, out
+
+
 def export_components(pmesh: PolygonMesh, verts, path: str, keep_largest: int = 0):
     """--components: which pieces the polygon surface (over our_mesh's scaled
     vertices `verts`) falls into and where its holes are; --keep-largest N
@@ -357,7 +411,7 @@ def train_sdf(net, args, path: str):
     epochs = args.epochs or (6 if "drill" == args.dataset else 10)  # train.py:67
     print(f"warning: cannot find a pretrained model for seed ({args.seed})! This training code is not "
           f"guarantee the convergence of training nor a reliable SDF.", flush=True)
-    training_data = StanfordDataset(args.dataset, mesh=args.mesh)
+    training_data = StanfordDataset(args.dataset, mesh=args.mesh, mesh_cell=args.mesh_cell)
     loader = torch.utils.data.DataLoader(training_data, batch_size=BATCH_SIZE, shuffle=True)
     trainer = SDFTrainer(net, lr=1e-3, T_max=epochs * len(training_data) / BATCH_SIZE, batch_size=BATCH_SIZE)
     result = None
@@ -420,6 +474,9 @@ def main(argv=None):
         poly_verts = verts
         if args.weld:
             pmesh, poly_path = export_welded(pmesh, verts, poly_path, args.weld)
+            poly_verts = pmesh.vertices
+        if args.simplify is not None:
+            pmesh, poly_path = export_simplified(pmesh, poly_verts, poly_path, args.simplify, args.simplify_position)
             poly_verts = pmesh.vertices
         topo = export_components(pmesh, poly_verts, poly_path, args.keep_largest)
         if args.fill_holes:
